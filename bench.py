@@ -72,6 +72,51 @@ STREAM_ELAPSED_NOTE = ("HIP-event brackets on the library's internal streams, su
                        "accumulate_busy_ms_per_step is the union of those two")
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """--dump-outputs: writes {name: array} as out_dir/<name>.npy in float64, for comparing two builds output for output.  Integer words
+    wider than 32 bits are split into their 32-bit halves first (little-endian, last axis doubled), so every value is exact in float64.
+    Past DUMP_BUDGET_BYTES in all, an array larger than its share is replaced by a fixed, seeded sample of its flattened elements, with
+    the sampled positions in <name>.index.npy.  Returns {name: shape written}."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype.kind in "ui" and a.dtype.itemsize > 4:
+            a = a.view(np.uint32 if a.dtype.kind == "u" else np.int32)
+        conv[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    share = DUMP_BUDGET_BYTES // max(1, len(conv))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in conv.items():
+        if total > DUMP_BUDGET_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(out_dir, name + ".index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
+def _output_arrays(x, prefix: str = "") -> dict:
+    """The numpy arrays of a prover's nested output (dicts / lists / tuples), named by their path: {"a.0.b": array}."""
+    if isinstance(x, dict):
+        items = ((str(k), x[k]) for k in sorted(x))
+    elif isinstance(x, (list, tuple)):
+        items = ((str(i), v) for i, v in enumerate(x))
+    elif isinstance(x, np.ndarray):
+        return {prefix: x}
+    else:
+        return {}
+    out = {}
+    for k, v in items:
+        out.update(_output_arrays(v, f"{prefix}.{k}" if prefix else k))
+    return out
+
+
 def busy_union_ms(ctxs, names) -> float:
     """Time during which at least one kernel bracket named in `names` was running, over all contexts in `ctxs` (their profile
     origins merged onto the first context's clock): the union of the HIP-event intervals, NOT the sum of elapsed times."""
@@ -911,6 +956,7 @@ def run_polyiop(args, czk, parallel, ctx, rank, world, n, size_txt):
             checked["timed_proof_verifies"] = True
     for o in outs[1:]:                                  # the other in-flight provers run the same deterministic inputs
         assert _polyiop_party_digests(o, lanes, 1, only=0) == _polyiop_party_digests(out, lanes, 1, only=0), "in-flight provers disagree"
+    dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, _output_arrays(out))} if args.dump_outputs and rank == 0 else None
     if party:
         mine = _polyiop_party_digests(out, lanes, 1, only=0)[0]
         got = [None] * world
@@ -956,6 +1002,8 @@ def run_polyiop(args, czk, parallel, ctx, rank, world, n, size_txt):
         "accumulate_busy_frac": busy_ms / (dt * 1e3), "accumulate_busy_ms_per_step": busy_ms / max(1, args.steps),
         "stream_elapsed_ms_per_step": {**breakdown, "note": STREAM_ELAPSED_NOTE}, "setup_srs_s": setup_s,
     }
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if rank == 0 and world == 1 and not party and not args.no_result_check and not args.no_verify_report:
         # The timed runs use work-shaped stand-in inputs (random polynomials / random index data), whose proofs cannot verify.  One more proof of the SAME
         # size on a satisfied circuit (Plonk) / a real index of a satisfied instance (Marlin), not timed, through the reference verifiers' equations
@@ -1177,7 +1225,12 @@ def main():
     ap.add_argument("--no-multi-gpu-report", action="store_true", help="--gpus N > 1, replica layout: skip the party / split layout children rank 0 runs after the replica line")
     ap.add_argument("--report-budget-s", type=float, default=240.0, help="wall-clock budget of the multi-GPU report; children that would start beyond it are skipped")
     ap.add_argument("--dry-run", action="store_true", help="launcher / process-group check only: no GPU work (CPU test of --gpus N)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                    "(float64; groth16: the affine MSM results of every share lane, integer words as 32-bit halves; plonk / marlin: every array of the "
+                    "prover's output) -- inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if args.layout == "party" and args.gpus != args.parties:
         raise SystemExit(f"--layout party needs one rank per party: --gpus {args.gpus}, --parties {args.parties}")
@@ -1301,6 +1354,14 @@ def main():
                 assert np.array_equal(aff[k][0], ref_aff[k][0]) and np.array_equal(aff[k][1], ref_aff[k][1]), f"pipelined proofs disagree on {k}"
     # MAC-check vectors of the two opens must be all zero (share/spdz.rs:176-183)
     assert args.scheme != "spdz" or not bool(prover.chk.any().item()), "SPDZ MAC check failed"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed proof's MSM results, in affine form: the Jacobian triples depend on the summation order inside buckets
+        last = {}
+        for k, v in prover.all_results[-1].items():
+            aff, inf = ctx.jac_to_affine(czk.CZK_G2 if k == "b_g2" else czk.CZK_G1, v)
+            last[k], last[k + ".infinity"] = aff, inf
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, last)}
     # ... and they must be the RIGHT group elements: host-side check against the bases' known discrete logs (every rank
     # checks its own lanes)
     checked = {"results_checked": False}
@@ -1482,6 +1543,8 @@ def main():
         "stream_elapsed_ms_per_step": {**breakdown, "note": STREAM_ELAPSED_NOTE},
         "setup_key_s": prover.setup_key_s,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if (rank == 0 and world == 1 and args.contexts_report > 1 and not party_layout and not split_layout and ref_aff is not None
             and not os.environ.get("CZK_BENCH_CHILD")):
         try:

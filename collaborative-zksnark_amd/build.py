@@ -31,7 +31,8 @@ HEADERS = ["field.h", "curve.h", "czk_internal.h", "msm_acc.h", "fq2p.h", "fq2pu
 LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-pass-failed", "-I" + CSRC]
-MAX_JOBS = int(os.environ.get("CZK_BUILD_JOBS", "0")) or max(4, (os.cpu_count() or 8))
+# parallel hipcc jobs: CZK_BUILD_JOBS, else the MAX_JOBS a build host sets (a container's os.cpu_count() is the whole machine's), else all cores
+MAX_JOBS = int(os.environ.get("CZK_BUILD_JOBS", "0")) or int(os.environ.get("MAX_JOBS", "0")) or max(4, (os.cpu_count() or 8))
 
 
 def _stale(target: str, deps: list[str]) -> bool:

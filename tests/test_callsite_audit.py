@@ -67,18 +67,25 @@ def test_drivers_emit_the_reference_call_sites(prover, size):
 
 
 def test_callsite_file_cites_existing_reference_lines():
-    """Where the reference tree is present (the build container), every cited file exists and has at least the cited lines."""
+    """Every cited file is in the stored index of the reference tree (tests/golden/reference_line_counts.json, written by
+    tests/golden/make_reference_index.py) and has at least the cited lines; where the reference tree is readable (the build
+    container), the index must be what the tree says."""
+    import hashlib
     import re
+    files = json.load(open(os.path.join(HERE, "golden", "reference_line_counts.json")))["files"]
     root = "/root/reference"
-    if not os.path.isdir(root):
-        pytest.skip("reference tree not present on this box")
+    for path, want in files.items():
+        full = os.path.join(root, path)
+        if os.access(full, os.R_OK):
+            data = open(full, "rb").read()
+            assert hashlib.sha256(data).hexdigest() == want["sha256"] and sum(1 for _ in open(full)) == want["lines"], \
+                f"{path} changed: python tests/golden/make_reference_index.py {root}"
     spec = json.load(open(os.path.join(HERE, "golden", "plonk_marlin_callsites.json")))
     n = 0
     for prover in ("plonk", "marlin"):
         for site in spec[prover]["sites"]:
             for path, line in re.findall(r"([\w\-/\.]+\.rs):(\d+)", site["ref"]):
-                full = os.path.join(root, path)
-                assert os.path.exists(full), path
-                assert sum(1 for _ in open(full)) >= int(line), (path, line)
+                assert path in files, path
+                assert files[path]["lines"] >= int(line), (path, line)
                 n += 1
     assert n > 80

@@ -160,3 +160,29 @@ def test_polyiop_party_digests_agree_between_layouts():
     replica = bench._polyiop_party_digests(full, lanes, parties)
     ranks = [bench._polyiop_party_digests(mine(full, p), per, 1, only=0)[0] for p in range(parties)]
     assert replica == ranks and replica[0] != replica[1]
+
+
+def test_bench_dump_outputs_are_exact_named_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: 64-bit words are written as their exact 32-bit halves in float64, nested prover outputs are named by
+    their path, and past the size budget a large array becomes the same seeded sample (values and positions) on every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(9)
+    words = rng.integers(0, 1 << 63, size=(4, 12), dtype=np.uint64) | np.uint64(1 << 63)
+    nested = {"h": words, "h.infinity": np.array([0, 1, 0, 0], np.uint8)}
+    assert set(bench._output_arrays({"cmt": (words, nested["h.infinity"]), "point": 5})) == {"cmt.0", "cmt.1"}
+    got = bench.dump_outputs(str(tmp_path / "a"), nested)
+    assert got == {"h": [4, 24], "h.infinity": [4]}
+    h = np.load(tmp_path / "a" / "h.npy")
+    assert h.dtype == np.float64 and np.array_equal(h.astype(np.uint64).astype(np.uint32).view(np.uint64), words)
+    assert np.array_equal(np.load(tmp_path / "a" / "h.infinity.npy"), [0.0, 1.0, 0.0, 0.0])
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    big = {"big": np.arange(10000, dtype=np.uint32), "small": np.arange(8, dtype=np.uint32)}
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), big) == {"big": [128], "small": [8]}
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) < 4096 + 4 * 128
+    for name in ("big.npy", "big.index.npy", "small.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / name), np.load(tmp_path / "c" / name))
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "b" / "big.index.npy"))
