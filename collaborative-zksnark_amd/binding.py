@@ -67,6 +67,7 @@ def _load(path):
     L.czk_net_destroy.restype = None
     L.czk_net_stats_reset.restype = None
     L.czk_sha256.restype = None
+    L.czk_groth16_pvk_release.restype = None
     return L
 
 
@@ -514,6 +515,56 @@ class Context:
         self._ck(self._L.czk_fixed_base_points(self._h, C.c_int(group), _ptr(k), C.c_size_t(n), _ptr(out), C.c_int(mem)))
         return out
 
+    # ---- pairing and Groth16 verification (czk_pairing*, czk_groth16_*) -----------------------------
+    def pairing(self, g1, g2, g1_inf=None, g2_inf=None):
+        """PairingEngine::pairing of n pairs: G1 (n, 12) and G2 (n, 24) affine Montgomery points -> (n, 72) Fq12 limbs."""
+        g1 = np.ascontiguousarray(g1, np.uint64).reshape(-1, 12)
+        g2 = np.ascontiguousarray(g2, np.uint64).reshape(-1, 24)
+        n = g1.shape[0]
+        assert g2.shape[0] == n
+        i1 = None if g1_inf is None else np.ascontiguousarray(g1_inf, np.uint8)
+        i2 = None if g2_inf is None else np.ascontiguousarray(g2_inf, np.uint8)
+        out = np.zeros((n, 72), dtype=np.uint64)
+        self._ck(self._L.czk_pairing(self._h, _ptr(g1), _ptr(i1), _ptr(g2), _ptr(i2), C.c_size_t(n), _ptr(out), C.c_int(CZK_MEM_HOST)))
+        return out
+
+    def pairing_product(self, g1, g2, offsets, g1_inf=None, g2_inf=None):
+        """PairingEngine::product_of_pairings of k = len(offsets) - 1 products over pairs [offsets[j], offsets[j+1]) -> ((k, 72), (k,) is-one flags)."""
+        g1 = np.ascontiguousarray(g1, np.uint64).reshape(-1, 12)
+        g2 = np.ascontiguousarray(g2, np.uint64).reshape(-1, 24)
+        offs = np.ascontiguousarray(offsets, np.uint64)
+        k = offs.size - 1
+        i1 = None if g1_inf is None else np.ascontiguousarray(g1_inf, np.uint8)
+        i2 = None if g2_inf is None else np.ascontiguousarray(g2_inf, np.uint8)
+        out = np.zeros((k, 72), dtype=np.uint64)
+        one = np.zeros(k, dtype=np.uint8)
+        self._ck(self._L.czk_pairing_product(self._h, _ptr(g1), _ptr(i1), _ptr(g2), _ptr(i2), _ptr(offs), C.c_size_t(k), _ptr(out), _ptr(one),
+                                             C.c_int(CZK_MEM_HOST)))
+        return out, one
+
+    def groth16_pvk(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, gamma_abc_inf=None):
+        """prepare_verifying_key on the GPU: a PreparedVerifyingKey handle (czk_groth16_pvk_create)."""
+        arrs = [np.ascontiguousarray(x, np.uint64) for x in (alpha_g1, beta_g2, gamma_g2, delta_g2)]
+        abc = np.ascontiguousarray(gamma_abc_g1, np.uint64).reshape(-1, 12)
+        inf = None if gamma_abc_inf is None else np.ascontiguousarray(gamma_abc_inf, np.uint8)
+        h = C.c_void_p()
+        self._ck(self._L.czk_groth16_pvk_create(self._h, *[_ptr(a) for a in arrs], _ptr(abc), _ptr(inf), C.c_size_t(abc.shape[0]), C.byref(h)))
+        return PreparedVerifyingKey(self, h, abc.shape[0])
+
+    def groth16_verify(self, pvk, a, b, c, public_inputs, inf=None):
+        """verify_proof over k proofs: a (k, 12), b (k, 24), c (k, 12), public_inputs (k, m, 4) Montgomery Fr, inf (k, 3) -> (k,) bool."""
+        a = np.ascontiguousarray(a, np.uint64).reshape(-1, 12)
+        k = a.shape[0]
+        b = np.ascontiguousarray(b, np.uint64).reshape(k, 24)
+        c = np.ascontiguousarray(c, np.uint64).reshape(k, 12)
+        x = np.ascontiguousarray(public_inputs, np.uint64).reshape(k, -1)
+        m = x.shape[1] // 4
+        inf = None if inf is None else np.ascontiguousarray(inf, np.uint8).reshape(k, 3)
+        ok = np.zeros(k, dtype=np.uint8)
+        self._ck(self._L.czk_groth16_verify(self._h, pvk._h, _ptr(a), _ptr(b), _ptr(c), _ptr(inf), _ptr(x if m else None), C.c_size_t(m),
+                                            C.c_size_t(k), _ptr(ok), C.c_int(CZK_MEM_HOST)))
+        return ok.astype(bool)
+
     # ---- measurement hooks ------------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._ck(self._L.czk_profile_enable(self._h, C.c_int(1 if on else 0)))
@@ -737,6 +788,24 @@ class R1csMatrix:
         if self._h:
             self.ctx._L.czk_r1cs_matrix_release(self._h)
             self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class PreparedVerifyingKey:
+    """czk_groth16_pvk: a Groth16 verifying key prepared on the GPU (e(alpha, beta), -gamma / -delta lines, gamma_abc_g1)."""
+
+    def __init__(self, ctx: Context, handle, n_gamma_abc: int):
+        self.ctx, self._h, self.n_gamma_abc = ctx, handle, n_gamma_abc
+
+    def release(self):
+        if self._h:
+            self.ctx._L.czk_groth16_pvk_release(self._h)
+            self._h = None
 
     def __del__(self):
         try:

@@ -512,6 +512,39 @@ int czk_fixed_base_points(czk_ctx* ctx, int group, const uint64_t* k, size_t n, 
 int czk_witness_map_pre(czk_ctx* ctx, uint64_t* a, size_t a_len, uint64_t* b, size_t b_len, unsigned log_d, size_t lanes);
 int czk_witness_map_post(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes);
 
+/* ---- pairing and Groth16 verification ------------------------------------------------------------ */
+/* The reference's pairing engine Bls12::<Parameters> (X = 0x8508c00000000001, TwistType::D; curves/bls12_377/src/curves/mod.rs:16-19,
+ * algebra/ec/src/models/bls12/mod.rs) on the GPU, one product of pairings per thread.  Points are affine Montgomery (G1: 12 u64, G2: 24 u64)
+ * plus infinity flags (NULL = none infinite); a pair with infinity on either side is skipped, as in miller_loop (mod.rs:99-103).
+ * GT elements: Fq12 = 72 u64 in the order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... c1.c2.c1 (Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - u)),
+ * each Fq 6 Montgomery limbs: bit for bit the reference's value.  No subgroup checks are made on any point.  All calls block.
+ *
+ * czk_pairing: PairingEngine::pairing (algebra/ec/src/lib.rs:111) of n independent pairs; out: n x 72 u64.
+ * czk_pairing_product: PairingEngine::product_of_pairings (lib.rs:102) of k products, product j over pairs [offsets[j], offsets[j+1]) of the
+ *   offsets[k] inputs; offsets (k + 1 entries, offsets[0] == 0, non-decreasing) are HOST memory whatever `mem` says.  out (k x 72) and
+ *   out_is_one (k flags: the product is one) may each be NULL.  An empty product is one.
+ * Buffers follow `mem` (CZK_MEM_HOST or CZK_MEM_DEVICE). */
+int czk_pairing(czk_ctx* ctx, const uint64_t* g1, const uint8_t* g1_inf, const uint64_t* g2, const uint8_t* g2_inf, size_t n, uint64_t* out, int mem);
+int czk_pairing_product(czk_ctx* ctx, const uint64_t* g1, const uint8_t* g1_inf, const uint64_t* g2, const uint8_t* g2_inf, const size_t* offsets,
+                        size_t k, uint64_t* out, uint8_t* out_is_one, int mem);
+
+/* prepare_verifying_key (groth16/src/verifier.rs:12-20) into device memory of the context's GPU: e(alpha, beta), -gamma and -delta
+ * prepared (G2Prepared, g2.rs:69-97), gamma_abc_g1.  Inputs are HOST memory: alpha (12 u64), beta / gamma / delta (24 u64 each, finite
+ * points), gamma_abc_g1 (n_gamma_abc x 12 u64, flags NULL = none infinite; n_gamma_abc >= 1).  The handle stays valid until
+ * czk_groth16_pvk_release and may be used by any context of the same device. */
+typedef struct czk_groth16_pvk czk_groth16_pvk;
+int czk_groth16_pvk_create(czk_ctx* ctx, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* gamma_g2, const uint64_t* delta_g2,
+                           const uint64_t* gamma_abc_g1, const uint8_t* gamma_abc_inf, size_t n_gamma_abc, czk_groth16_pvk** out);
+void czk_groth16_pvk_release(czk_groth16_pvk* pvk);
+/* verify_proof (verifier.rs:23-58) over k proofs: out_ok[j] = 1 iff e(A, B) e(g_ic, -gamma) e(C, -delta) == e(alpha, beta) with
+ * g_ic = gamma_abc[0] + sum_i x_i gamma_abc[i + 1] -- one Miller loop over the three pairs and one final exponentiation per proof (the
+ * same decision as the reference's three pairings: the final exponentiation is a homomorphism).  a: k x 12, b: k x 24, c: k x 12 u64;
+ * inf: k x 3 flags (A, B, C; NULL = none infinite); public_inputs: k x m x 4 u64, Montgomery Fr (as E::Fr).  m + 1 != n_gamma_abc is
+ * CZK_ERR_ARG "MalformedVerifyingKey" (verifier.rs:28-30).  As in verify_proof, the proof's points get NO subgroup or on-curve check.
+ * Buffers follow `mem`. */
+int czk_groth16_verify(czk_ctx* ctx, const czk_groth16_pvk* pvk, const uint64_t* a, const uint64_t* b, const uint64_t* c, const uint8_t* inf,
+                       const uint64_t* public_inputs, size_t m, size_t k, uint8_t* out_ok, int mem);
+
 /* ---- measurement hooks --------------------------------------------------------------------------- */
 /* When enabled, the library brackets its kernel launches with HIP events on the context's stream (the stream the
  * kernels run on) and accumulates per-kernel elapsed time.  Names: "msm_accumulate_g1", "msm_accumulate_g2",

@@ -29,6 +29,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <optional>
@@ -602,5 +603,76 @@ struct R1CStoQAP {
         ab.len = c.len = domain.size();
     }
 };
+
+// ---- pairing and Groth16 verification (czk_pairing*, czk_groth16_*) ------------------------------------------------------------
+//   Bls12::<Parameters>::pairing / product_of_pairings (algebra/ec/src/lib.rs:102-116)     Bls12_377::pairing / product_of_pairings
+//   prepare_verifying_key, verify_proof (groth16/src/verifier.rs:12-58)                    prepare_verifying_key, verify_proof
+struct Fq6 { Fq2 c0, c1, c2; };
+struct Fq12 { Fq6 c0, c1; };   // 72 u64, the reference's nesting (czk.h)
+struct G1AffinePoint { Fq x, y; bool infinity = false; };
+struct G2AffinePoint { Fq2 x, y; bool infinity = false; };
+
+struct Bls12_377 {
+    static Fq12 product_of_pairings(const Context& ctx, const std::vector<std::pair<G1AffinePoint, G2AffinePoint>>& pairs) {
+        std::vector<uint64_t> g1(pairs.size() * 12), g2(pairs.size() * 24);
+        std::vector<uint8_t> i1(pairs.size()), i2(pairs.size());
+        for (size_t i = 0; i < pairs.size(); i++) {
+            std::memcpy(&g1[12 * i], &pairs[i].first.x, 96);
+            std::memcpy(&g2[24 * i], &pairs[i].second.x, 192);
+            i1[i] = pairs[i].first.infinity;
+            i2[i] = pairs[i].second.infinity;
+        }
+        const size_t offs[2] = {0, pairs.size()};
+        Fq12 out;
+        ctx.check(czk_pairing_product(ctx.raw(), g1.data(), i1.data(), g2.data(), i2.data(), offs, 1, &out.c0.c0.c0.l[0], nullptr, CZK_MEM_HOST));
+        return out;
+    }
+    static Fq12 pairing(const Context& ctx, const G1AffinePoint& p, const G2AffinePoint& q) { return product_of_pairings(ctx, {{p, q}}); }
+};
+
+struct VerifyingKey {
+    G1AffinePoint alpha_g1;
+    G2AffinePoint beta_g2, gamma_g2, delta_g2;
+    std::vector<G1AffinePoint> gamma_abc_g1;
+};
+struct Proof {
+    G1AffinePoint a;
+    G2AffinePoint b;
+    G1AffinePoint c;
+};
+
+// e(alpha, beta), -gamma / -delta prepared and gamma_abc_g1, resident on the context's GPU
+class PreparedVerifyingKey {
+  public:
+    PreparedVerifyingKey(const Context& ctx, const VerifyingKey& vk) : ctx_(&ctx) {
+        std::vector<uint64_t> abc(vk.gamma_abc_g1.size() * 12);
+        std::vector<uint8_t> inf(vk.gamma_abc_g1.size());
+        for (size_t i = 0; i < vk.gamma_abc_g1.size(); i++) {
+            std::memcpy(&abc[12 * i], &vk.gamma_abc_g1[i].x, 96);
+            inf[i] = vk.gamma_abc_g1[i].infinity;
+        }
+        ctx.check(czk_groth16_pvk_create(ctx.raw(), vk.alpha_g1.x.l, vk.beta_g2.x.c0.l, vk.gamma_g2.x.c0.l, vk.delta_g2.x.c0.l, abc.data(), inf.data(),
+                                         abc.size() / 12, &pvk_));
+    }
+    ~PreparedVerifyingKey() { czk_groth16_pvk_release(pvk_); }
+    PreparedVerifyingKey(const PreparedVerifyingKey&) = delete;
+    PreparedVerifyingKey& operator=(const PreparedVerifyingKey&) = delete;
+    const Context& ctx() const { return *ctx_; }
+    const czk_groth16_pvk* raw() const { return pvk_; }
+
+  private:
+    const Context* ctx_;
+    czk_groth16_pvk* pvk_ = nullptr;
+};
+inline std::unique_ptr<PreparedVerifyingKey> prepare_verifying_key(const Context& ctx, const VerifyingKey& vk) {
+    return std::make_unique<PreparedVerifyingKey>(ctx, vk);
+}
+// verifier.rs:23-58; a wrong number of public inputs panics (Panic, CZK_ERR_ARG "MalformedVerifyingKey")
+inline bool verify_proof(const PreparedVerifyingKey& pvk, const Proof& proof, const std::vector<Fr>& public_inputs) {
+    uint8_t inf[3] = {proof.a.infinity, proof.b.infinity, proof.c.infinity}, ok = 0;
+    pvk.ctx().check(czk_groth16_verify(pvk.ctx().raw(), pvk.raw(), proof.a.x.l, proof.b.x.c0.l, proof.c.x.l, inf,
+                                       public_inputs.empty() ? nullptr : public_inputs[0].l, public_inputs.size(), 1, &ok, CZK_MEM_HOST));
+    return ok != 0;
+}
 
 }  // namespace czk

@@ -23,6 +23,10 @@ pub struct czk_net {
 pub struct czk_r1cs_matrix {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct czk_groth16_pvk {
+    _private: [u8; 0],
+}
 
 pub const CZK_OK: c_int = 0; // czk_status
 pub const CZK_ERR_SIZE: c_int = 1; // czk_status
@@ -149,6 +153,11 @@ extern "C" {
     pub fn czk_fixed_base_points(ctx: *mut czk_ctx, group: c_int, k: *const u64, n: usize, out: *mut u64, mem: c_int) -> c_int;
     pub fn czk_witness_map_pre(ctx: *mut czk_ctx, a: *mut u64, a_len: usize, b: *mut u64, b_len: usize, log_d: c_uint, lanes: usize) -> c_int;
     pub fn czk_witness_map_post(ctx: *mut czk_ctx, ab: *mut u64, c: *mut u64, c_len: usize, log_d: c_uint, lanes: usize) -> c_int;
+    pub fn czk_pairing(ctx: *mut czk_ctx, g1: *const u64, g1_inf: *const u8, g2: *const u64, g2_inf: *const u8, n: usize, out: *mut u64, mem: c_int) -> c_int;
+    pub fn czk_pairing_product(ctx: *mut czk_ctx, g1: *const u64, g1_inf: *const u8, g2: *const u64, g2_inf: *const u8, offsets: *const usize, k: usize, out: *mut u64, out_is_one: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_groth16_pvk_create(ctx: *mut czk_ctx, alpha_g1: *const u64, beta_g2: *const u64, gamma_g2: *const u64, delta_g2: *const u64, gamma_abc_g1: *const u64, gamma_abc_inf: *const u8, n_gamma_abc: usize, out: *mut *mut czk_groth16_pvk) -> c_int;
+    pub fn czk_groth16_pvk_release(pvk: *mut czk_groth16_pvk);
+    pub fn czk_groth16_verify(ctx: *mut czk_ctx, pvk: *const czk_groth16_pvk, a: *const u64, b: *const u64, c: *const u64, inf: *const u8, public_inputs: *const u64, m: usize, k: usize, out_ok: *mut u8, mem: c_int) -> c_int;
     pub fn czk_profile_enable(ctx: *mut czk_ctx, on: c_int) -> c_int;
     pub fn czk_profile_reset(ctx: *mut czk_ctx) -> c_int;
     pub fn czk_profile_read(ctx: *mut czk_ctx, kernel: *const c_char, total_ms: *mut f64, launches: *mut u64) -> c_int;
