@@ -13,9 +13,16 @@ data-path collective: parties and proofs are independent units, SURVEY.md sectio
 max-over-ranks time.  Layout "party": ONE proof, party p on rank p (N == --parties), opens all-gathered over RCCL.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (G1 bucket accumulation), timed live with
-HIP events on the stream it runs on; `cpu_baseline` times the CPU checker (oracle/, the C restatement of the
-reference algorithms) -- one thread on a bounded sample and all host cores; after the timed region every MSM result is
-checked against [sum_i k_i s_i] G computed on the host from the known discrete logs of the bases (`results_checked`).
+HIP events on the stream it runs on.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+`--full` adds everything else, each leg still switched off by its own --no-* option: after the timed region every MSM
+result is checked against [sum_i k_i s_i] G computed on the host from the known discrete logs of the bases
+(`results_checked`) and all pipelined proofs are compared; one proof under a real key goes through the verification
+equation (`proof_verifies`); the seam and one-shot reports; the other BASELINE workloads as child runs
+(`other_workloads`); `cpu_baseline` times the CPU checker (oracle/, the C restatement of the reference algorithms) --
+one thread on a bounded sample and all host cores; and on N > 1 GPUs the party / split layout children
+(`multi_gpu_report`).
 """
 from __future__ import annotations
 
@@ -259,7 +266,7 @@ def other_workloads_report(device: int) -> dict:
             continue
         t0 = time.time()
         try:
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", str(device), "--no-cpu-baseline", "--no-other-workloads"] + argv,
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", str(device), "--full", "--no-cpu-baseline", "--no-other-workloads"] + argv,
                                capture_output=True, text=True, timeout=600,
                                env={**{k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}, "CZK_BENCH_CHILD": "1"})
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -423,7 +430,7 @@ def multi_gpu_report(n: int, headline: dict, dry_run: bool, budget_s: float) -> 
         if left < 30:
             out[key] = {"skipped": f"report budget of {budget_s:.0f} s used up"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-workloads", "--no-multi-gpu-report", "--no-verify-report"] + argv + (["--dry-run"] if dry_run else [])
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-workloads", "--no-multi-gpu-report", "--no-verify-report"] + argv + (["--dry-run"] if dry_run else [])
         t0 = time.time()
         try:
             rc, c_out, c_err = _run_child(cmd, env, min(420.0, left))
@@ -954,7 +961,7 @@ def run_polyiop(args, czk, parallel, ctx, rank, world, n, size_txt):
         if not plonk:
             marlin_verify(polyvm, out)
             checked["timed_proof_verifies"] = True
-    for o in outs[1:]:                                  # the other in-flight provers run the same deterministic inputs
+    for o in (outs[1:] if args.full else []):           # the other in-flight provers run the same deterministic inputs
         assert _polyiop_party_digests(o, lanes, 1, only=0) == _polyiop_party_digests(out, lanes, 1, only=0), "in-flight provers disagree"
     dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, _output_arrays(out))} if args.dump_outputs and rank == 0 else None
     if party:
@@ -1180,10 +1187,10 @@ def main():
     ap.add_argument("--no-seam-report", action="store_true")
     ap.add_argument("--real-key", action="store_true", help="groth16, any layout: prove under a REAL key (discrete logs from known toxic waste, tests/groth16_real_key.py) and put the "
                                                            "opened proof through the verification equation (`proof_verifies`; in the party layout the parties' shares are gathered on rank 0) "
-                                                           "instead of the discrete-log check of the synthetic key")
+                                                           "instead of the discrete-log check of the synthetic key; the check runs with --full")
     ap.add_argument("--real-instance", action="store_true", help="plonk / marlin: time the prover on a SATISFIED circuit / a real index of a satisfied instance (tests/polyiop_real.py) instead of "
-                                                                "the work-shaped stand-ins; marlin: the timed proofs themselves go through the AHP verifier's decision")
-    ap.add_argument("--verify-report", action="store_true", help="run the `proof_verifies` leg even as a child of another bench.py (the `other_workloads` entries of configs[0])")
+                                                                "the work-shaped stand-ins; marlin, with --full: the timed proofs themselves go through the AHP verifier's decision")
+    ap.add_argument("--verify-report", action="store_true", help="with --full: run the `proof_verifies` leg even as a child of another bench.py (the `other_workloads` entries of configs[0])")
     ap.add_argument("--no-verify-report", action="store_true", help="skip `proof_verifies`: one proof of this configuration under a real key against the Groth16 verification equation")
     ap.add_argument("--workload", choices=("groth16", "plonk", "marlin"), default="groth16",
                     help="groth16 (default; BASELINE metric, SPDZ lanes); plonk: mpc-plonk's prover, GSZ lanes, --log-n = log2(gates) (configs[2]: "
@@ -1228,9 +1235,15 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
                     "(float64; groth16: the affine MSM results of every share lane, integer words as 32-bit halves; plonk / marlin: every array of the "
                     "prover's output) -- inputs are seeded, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need, each leg still subject to its --no-* option: the host-side "
+                    "result checks, `proof_verifies`, the seam / one-shot reports, `other_workloads`, `cpu_baseline` and, on N > 1 GPUs, `multi_gpu_report` "
+                    "(default off: a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line)")
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("bench.py: --steps must be at least 1")
+    if not args.full:
+        args.no_result_check = args.no_verify_report = args.no_seam_report = True
+        args.no_other_workloads = args.no_cpu_baseline = args.no_multi_gpu_report = True
 
     if args.layout == "party" and args.gpus != args.parties:
         raise SystemExit(f"--layout party needs one rank per party: --gpus {args.gpus}, --parties {args.parties}")
@@ -1343,9 +1356,10 @@ def main():
             args.no_result_check = True
 
     # every pipelined proof works on the same inputs, so all of them must yield the same group elements (compared in
-    # affine: summation order inside buckets is not deterministic, Jacobian triples differ) -- guards the pipelining
+    # affine: summation order inside buckets is not deterministic, Jacobian triples differ) -- guards the pipelining.
+    # A plain run converts the first proof only, for the digest.
     ref_aff = None
-    for r in (prover.all_results if (rank == 0 or not split_layout) else []):
+    for r in ((prover.all_results if args.full else prover.all_results[:1]) if (rank == 0 or not split_layout) else []):
         aff = {k: ctx.jac_to_affine(czk.CZK_G2 if k == "b_g2" else czk.CZK_G1, v) for k, v in r.items()}
         if ref_aff is None:
             ref_aff = aff
@@ -1379,7 +1393,7 @@ def main():
         mine = b"".join(g[k] for k in ("h", "l", "a", "b_g1", "b_g2") for g in gathered)
     digest = hashlib.sha256(mine).hexdigest()
     real_key_report = None
-    if rk is not None:
+    if rk is not None and args.full:
         # the last proof of the timed region, opened and verified: every rank contributes its local parties' sh-lane shares of Proof{a, b, c} and its lanes'
         # part of the h MSM's exponent; rank 0 adds them up (party layout: gathered over the process group; split layout: rank 0 holds the combined sums)
         from groth16_real_key import R_INV
@@ -1555,6 +1569,7 @@ def main():
             torch.cuda.empty_cache()
     if real_key_report is not None:
         out["proof_verifies"] = real_key_report
+    if rk is not None:
         out["data"] = "synthetic circuit, REAL proving key (known toxic waste)"
     if rank == 0 and world == 1 and not args.no_seam_report and args.scheme == "spdz":
         t = prover.seam_calls_host_memory()

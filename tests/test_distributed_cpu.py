@@ -92,14 +92,14 @@ def test_bench_launcher_starts_one_rank_per_gpu(gpus, layout):
 
 @pytest.mark.parametrize("gpus", [2, 3])
 def test_multi_gpu_report_shape(gpus):
-    """`bench.py --gpus N` on N > 1 GPUs (the driver's SCALE run) follows its replica line with the party / split layout children
+    """`bench.py --gpus N --full` on N > 1 GPUs follows its replica line with the party / split layout children
     (bench.multi_gpu_report); --dry-run produces the report's shape on CPU: one launch per kind of child (one-GPU reference, party layout
     over N ranks, the Groth16 party layout under a real key with `proof_verifies`, split layout over N ranks), the rest as planned commands.  Every party child names the one-GPU run whose digest it must
     reproduce, covers both exchange patterns and both transports, and the config is the BASELINE one whose party count is N."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-run"], capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-run", "--full"], capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                        # ONE JSON line, whatever the children print
@@ -121,6 +121,19 @@ def test_multi_gpu_report_shape(gpus):
         assert v["n_gpus"] == want and v["ranks_seen_by_backend"] == want, (k, v)
     assert rep["groth16_spdz2_2e20/split"]["reference"] == "headline"
     assert not any("error" in v for v in rep.values()), rep
+
+
+def test_plain_bench_run_has_no_multi_gpu_report():
+    """Without --full, `bench.py --gpus N` prints the replica line alone: the party / split layout children are part of --full."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["dry_run"] and d["n_gpus"] == 2 and "multi_gpu_report" not in d
 
 
 def test_bench_refuses_a_world_size_that_is_not_gpus():

@@ -776,7 +776,7 @@ def test_party_per_rank_layout_matches_single_gpu_layout(parties, size):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = size + ["--parties", str(parties), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-seam-report"]
+    common = size + ["--parties", str(parties), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-seam-report"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True, timeout=280, env=env, cwd=root)
@@ -802,7 +802,7 @@ def test_party_layout_under_the_other_sharings(scheme, parties, net):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--constraints", "1000", "--parties", str(parties), "--scheme", scheme, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-seam-report",
+    common = ["--constraints", "1000", "--parties", str(parties), "--scheme", scheme, "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-seam-report",
               "--no-other-workloads"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
@@ -1772,7 +1772,7 @@ def test_groth16_intra_party_split_matches_the_one_gpu_layout(ranks, size):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = size + ["--parties", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-seam-report", "--no-other-workloads"]
+    common = size + ["--parties", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-seam-report", "--no-other-workloads"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True, timeout=280, env=env, cwd=root)

@@ -421,7 +421,7 @@ def test_cpp_party_layout_yields_the_digest_of_every_other_layout(world, size, e
     assert cpp_party["king_net_stats"]["broadcasts"] == 2 * 2 * per_open
     cpp_one = _json_tail(subprocess.run([exe, "bench", "--parties", str(world), "--steps", "2", "--warmup", "1"] + size + tables,
                                         capture_output=True, text=True, timeout=600, env=env))
-    common = size + tables + ["--parties", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-seam-report", "--no-other-workloads"]
+    common = size + tables + ["--parties", str(world), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-seam-report", "--no-other-workloads"]
     py_one = _json_tail(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT))
     py_party = _json_tail(__import__('util').run_ranks([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--layout", "party", "--backend", "gloo", "--device", "0"]
                                          + common, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT))

@@ -79,7 +79,7 @@ def test_party_per_rank_layout_of_the_polynomial_provers_matches_the_one_gpu_lay
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--workload", workload, "--parties", str(parties), "--constraints", str(constraints), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--workload", workload, "--parties", str(parties), "--constraints", str(constraints), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True, timeout=280, env=env, cwd=root)

@@ -140,7 +140,7 @@ def test_bench_real_key_proof_verifies_in_every_layout(argv):
     import sys
     import util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py")] + argv + ["--real-key", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-seam-report", "--no-other-workloads"]
+    cmd = [sys.executable, os.path.join(root, "bench.py")] + argv + ["--real-key", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-seam-report", "--no-other-workloads"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     run = util.run_ranks if "--gpus" in argv else subprocess.run
