@@ -109,6 +109,25 @@ def _ptr(x):
     return C.c_void_p(int(x))
 
 
+# enum czk_lab_arith_op of csrc/lab/arith_probe.h: name -> (op, input words per item, output words per item)
+LAB_ARITH_PROBE_OPS = {
+    "fqu_mul": (0, 28, 14), "fqu_sqr": (1, 14, 14), "fqu_mul_add": (2, 56, 14), "fqu_mul_add_hi": (3, 70, 14), "fqu_mul_hi": (4, 42, 14),
+    "fqu_mul_add4": (5, 112, 14), "fqu_normalize": (6, 14, 14), "fqu_sub_lazy<4>": (7, 28, 14), "fqu_sub_lazy<8>": (8, 28, 14),
+    "fqu_sub_lazy<16>": (9, 28, 14), "fqu_sub3_norm": (10, 42, 14), "fqu_unpack": (11, 12, 14), "fqu_pack": (12, 14, 12),
+    "fqu_neg5<false>": (13, 14, 14), "fqu_neg5<true>": (14, 14, 14), "fqu_add_lazy": (15, 28, 14), "fqu_subn_32": (16, 28, 14),
+    "fqu_subn_64": (17, 28, 14), "fqu_subn_128": (18, 28, 14),
+    "fq2u_mul": (20, 56, 28), "fq2u_sqr": (21, 28, 28), "fq2u_mul_n5": (22, 56, 28),
+    "fqu_xyzz_acc_mixed": (30, 84, 57), "xyzzu_add": (31, 114, 57), "xyzzu_double": (32, 57, 57), "xyzzu_to_sat": (33, 57, 48),
+    "xyzzu_from_sat": (34, 48, 57), "fq2u_xyzz_acc_mixed": (35, 168, 113),
+    "teu_from_niels": (40, 42, 56), "teu_madd": (41, 98, 56), "teu_add": (42, 112, 56), "teu_double": (43, 56, 56), "teu_to_jac": (44, 56, 36),
+    "te_load_niels": (45, 52, 42),
+    "p2_mul": (50, 57, 28), "xyzzu2_add": (51, 226, 113), "xyzzu2_double": (52, 113, 113), "xyzzu2_acc_mixed": (53, 168, 113),
+    "fru_mul": (60, 18, 9), "fru_normalize": (62, 9, 9), "fru_unpack": (63, 8, 9), "fru_pack": (64, 9, 8), "fru_reduce_2r": (65, 9, 9),
+    "fru_canon": (66, 9, 8), "fru_canon_mulout": (67, 9, 8), "fru_add": (68, 18, 9),
+}
+LAB_ARITH_PROBE_OPS.update({f"fru_sub<{1 << lg},{u}>": (100 + 2 * lg + (u - 1), 18, 9) for lg in range(1, 9) for u in (1, 2)})
+
+
 class Context:
     """czk_ctx: one GPU + one HIP stream = one MPC party.
 
@@ -120,6 +139,7 @@ class Context:
         """lab=True binds this context to libczk_hip_lab.so (tests / A/B tools: the rejected kernel variants and their options);
         `options`: {name: value} passed to czk_ctx_set_option before any work."""
         self._L = lab_lib() if lab else lib()
+        self._lab = bool(lab)
         self._h = C.c_void_p(0)
         rc = self._L.czk_ctx_create(C.byref(self._h), C.c_int(device), C.c_void_p(stream or 0))
         if rc:
@@ -138,6 +158,21 @@ class Context:
 
     def set_option(self, name: str, value: int):
         self._ck(self._L.czk_ctx_set_option(self._h, name.encode(), C.c_long(int(value))))
+
+    def lab_arith_probe(self, op: str, items):
+        """czk_lab_arith_probe (csrc/lab/arith_probe.h, lab library only): runs the function named `op` (a key of LAB_ARITH_PROBE_OPS)
+        of the unsaturated arithmetic headers once per row of `items` -- raw u32 limbs exactly as given -- and returns the raw result
+        rows.  Raises unless the context was opened with lab=True: the product library does not carry the probe."""
+        if not self._lab:
+            raise RuntimeError("lab_arith_probe needs Context(lab=True): libczk_hip.so does not export czk_lab_arith_probe")
+        code, iw, ow = LAB_ARITH_PROBE_OPS[op]
+        a = np.ascontiguousarray(items, dtype=np.uint32)
+        if a.ndim != 2 or a.shape[1] != iw:
+            raise ValueError(f"{op} takes {iw} words per item, got an array of shape {a.shape}")
+        out = np.zeros((a.shape[0], ow), dtype=np.uint32)
+        self._ck(self._L.czk_lab_arith_probe(self._h, C.c_int(code), _ptr(a), C.c_size_t(iw), _ptr(out), C.c_size_t(ow), C.c_size_t(a.shape[0]),
+                                             C.c_int(CZK_MEM_HOST)))
+        return out
 
     def close(self):
         if self._h:

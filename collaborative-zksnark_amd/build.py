@@ -5,8 +5,10 @@
   libczk_hip_lab.so  the LAB build (-DCZK_LAB): the same sources plus the measured-and-rejected variants kept for A/B runs (csrc/lab/:
                      batched-affine rounds, safegcd inversion, interleaved multiply-add chains, Karatsuba Fq2; the lane-pair G2 accumulate
                      kernel, the saturated accumulate / reduction kernels) and the CZK_* environment switches of the measurement tools,
-                     which it translates into options.  Same exported symbols.  Loaded by tests through Context(lab=True) and by tools
-                     through CZK_LIB_PATH; never by the provers.
+                     which it translates into options.  Every ABI symbol, plus the probe: csrc/lab/arith_probe.hip (LAB_SOURCES) exports
+                     czk_lab_arith_probe, which runs one function of the unsaturated arithmetic headers on raw limbs for
+                     tests/test_lazy_arith.py.  Loaded by tests through Context(lab=True) and by tools through CZK_LIB_PATH; never by
+                     the provers.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container as well as on the GPU box.
 """
@@ -27,9 +29,11 @@ LIB_LAB = os.path.join(HERE, "libczk_hip_lab.so")
 SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_MUL"]), ("ntt.hip", []), ("ntt_pass.hip", []), ("ntt_mixed.hip", []), ("msm.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_acc_g1.hip", []),
            ("msm_acc_g2.hip", []), ("msm_red_g2.hip", []), ("msm_heavy_g2.hip", []), ("poly.hip", []), ("share.hip", []), ("net.hip", ["-DCZK_NOINLINE_MUL"]),
            ("pairing.hip", ["-DCZK_NOINLINE_MUL"])]
+# lab library only: never compiled into, nor linked with, the product library
+LAB_SOURCES = [(os.path.join("lab", "arith_probe.hip"), [])]
 HEADERS = ["field.h", "curve.h", "czk_internal.h", "msm_acc.h", "fq2p.h", "fq2pu.h", "fqu.h", "fru.h", "fru_constants.inc", "ntt_pass.h", "te.h", "te_constants.inc", "tower.h", "pairing_constants.inc",
            os.path.join("..", "..", "include", "czk.h")]
-LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h")]
+LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h", "arith_probe.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-pass-failed", "-I" + CSRC]
 # parallel hipcc jobs: CZK_BUILD_JOBS, else the MAX_JOBS a build host sets (a container's os.cpu_count() is the whole machine's), else all cores
@@ -48,9 +52,9 @@ def _plan(lab: bool, force: bool):
     objdir = os.path.join(CSRC, "obj_lab" if lab else "obj")
     os.makedirs(objdir, exist_ok=True)
     objs, jobs = [], []
-    for src, extra in SOURCES:
+    for src, extra in SOURCES + (LAB_SOURCES if lab else []):
         s = os.path.join(CSRC, src)
-        o = os.path.join(objdir, src.replace(".hip", ".o"))
+        o = os.path.join(objdir, os.path.basename(src).replace(".hip", ".o"))
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
             jobs.append([HIPCC] + FLAGS + extra + (["-DCZK_LAB"] if lab else []) + ["-c", s, "-o", o])

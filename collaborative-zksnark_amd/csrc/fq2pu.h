@@ -11,9 +11,9 @@
 // Values are the same field elements as Fq2's; coordinates are kept in "u-form" (value * 2^392 mod p + k p, packed 12 x u32 per half)
 // from k_accumulate_u2's store to the last step, where the result is converted to the reference's Jacobian triple in Montgomery form.
 //
-// Value discipline (units of p; every value normalised, limbs < 2^28): inputs x < 100, y < 36, zz, zzz < 3.2 (k_accumulate_u2's
+// Value discipline (units of p; every value normalised, limbs < 2^28): inputs x < 100, y < 36, zz, zzz < 3.19 (fqu_neg5<false>'s limit; k_accumulate_u2's
 // buckets: x < 85, y < 36, zz, zzz < 3; sums of this file: x < 9.2, the rest < 1.2).  A product's output is below
-// 1.01 + (|a| |b| + |a| |Y|) / 38968 with |Y| <= 16 (small multipliers, < 3.2) or 512 (multipliers up to 102): < 1.2 everywhere but
+// 1.01 + (|a| |b| + |a| |Y|) / 38968 with |Y| <= 16 (small multipliers, < 3.19) or 512 (multipliers up to 102): < 1.2 everywhere but
 // for V = (2 Y1)^2 (< 2.1) and X1^2 (< 2.6) of the doubling.
 #pragma once
 #include "fq2p.h"
@@ -40,7 +40,7 @@ struct P2B {   // multiplier, normalised: even lane (b0, K p - 5 b1), odd lane (
     FqU x, y;
 };
 __device__ __forceinline__ P2A p2_a(const FqU& a) { return P2A{a, pair_swap_u(a)}; }
-// BIG: the multiplier's value may reach 102 p (K = 512); otherwise it is below 3.2 p (K = 16)
+// BIG: the multiplier's value may reach 102 p (K = 512); otherwise it is below 3.19 p (K = 16)
 template <bool BIG>
 __device__ __forceinline__ P2B p2_b(const FqU& b) {
     const bool par = pair_parity();
@@ -206,7 +206,7 @@ __device__ __forceinline__ void xyzzu2_double(XYZZU2& a) {
 // inside the Groth16 pipeline -- and the PROOF gets slower (78.7 - 81.3 against 76.2 - 77.6 ms, any MSM order): two such waves leave no room for
 // the NTT / sort / reduction waves that run beside the single-lane kernel's one wave, the accumulate stream then waits for them, and the machine's
 // instruction throughput was already used either way (profiles/r03_g2_lane_pairs.txt).  Not adopted; the default stays k_accumulate_u2.
-// Bounds (units of p): ax < 9.2 after an addition (a first point's < 1), ay < 4, azz, azzz < 3.2; qx canonical; qy canonical or the lazy
+// Bounds (units of p): ax < 9.2 after an addition (a first point's < 1), ay < 4, azz, azzz < 3.19; qx canonical; qy canonical or the lazy
 // 4 p - y of a negated point.  H = U2 - X1 + 16 p: each half in (6.8, 17.2); it is 0 mod p only if it equals j p, j in 7..17, i.e. its low limb
 // is j -- returns false when both halves look like that (the caller defers the point to the saturated complete formulas).
 __device__ __forceinline__ bool xyzzu2_acc_mixed(FqU& ax, FqU& ay, FqU& azz, FqU& azzz, const FqU& qx, const FqU& qy) {

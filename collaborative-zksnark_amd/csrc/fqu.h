@@ -7,6 +7,9 @@
 // let additions and subtractions stay LAZY: a multiply accepts operands up to 2^7 p with limbs < 2^30 and returns
 // a value < 1.01 p with normalised limbs (no final subtraction), so only the two stored accumulator coordinates
 // are re-normalised per mixed addition.  ~486 instructions per multiply against ~620.
+// (2^7 p is the discipline of the G1 / twisted Edwards formulas, not a limit of the multiply: it is exact for any limbs < 2^30 whose
+// product keeps the result, < a b / 2^392 + p, inside the limb form.  The Fq2 code below feeds it values up to 512 p and tracks its outputs
+// instead, all < 26 p.  tests/lazy_model.py states both disciplines; tests/test_lazy_arith_cpu.py proves every formula closed under its own.)
 //
 // Values: a field element a is held as a * R' mod p (+ a multiple of p when lazy).  Bases are converted once at
 // registration (multiply by R' mod p in the saturated form, stored as canonical 12 x u32 integers); bucket results
@@ -971,6 +974,8 @@ __device__ __forceinline__ void xyzzu_double(XYZZU& a) {
 // add / sub (limbs < 2^28), so only VALUE bounds need tracking; the lazy-subtraction constants below (K p in
 // redundant limb form, generated) were chosen with an interval analysis of the whole mixed addition -- stable
 // bounds: X < 85 p, Y < 49 p, H < 145 p, r < 81 p, every multiply output < 26 p, capacity 2^392 = 38968 p.
+// (These are loose upper bounds of that analysis.  The figures in fq2u_xyzz_acc_mixed's own comment -- Y < 36 p, H in (43, 131) p, r < 67 p --
+// are the ones the formula re-establishes, and the ones tests/test_lazy_arith_cpu.py proves closed.)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 fqu_8p_u2(int i) {   // 8 p, every limb but the top >= 2 * 2^28
     constexpr u32 m[14] = {0x20000008u, 0x245ffffeu, 0x20000426u, 0x2ea217feu, 0x2000b858u, 0x27dd04a2u, 0x28f79b0fu,
@@ -1074,7 +1079,8 @@ __device__ __forceinline__ u32 fqu_512p_u5(int i) {   // 512 p, every limb but t
                            0x5ea271deu, 0x55b3e5fcu, 0x5927633fu, 0x5b80d93du, 0x5d58c75bu, 0x5c2f8a1cu, 0x0035c743u};
     return m[i];
 }
-// K p - 5 a, normalised (K = 16: a < 3.2 p; K = 512: a < 102 p): the beta * a1 operand of the schoolbook product below
+// K p - 5 a, normalised (K = 16: a < 3.19 p; K = 512: a < 102 p -- exactly: 5 x the top limb of a must not exceed the table's top limb, which
+// a value in the last 0.0001 p below 3.2 p misses): the beta * a1 operand of the schoolbook product below
 template <bool BIG>
 __device__ __forceinline__ FqU fqu_neg5(const FqU& a) {
     FqU r;

@@ -152,8 +152,8 @@ def test_host_side_field_code_matches_checker(orc):
 
 def test_product_library_has_no_environment_switches_and_no_lab_kernels():
     """libczk_hip.so (what a prover links) imports no getenv and carries none of the measured-and-rejected kernel
-    variants; libczk_hip_lab.so (tests / A/B tools) is the same source with -DCZK_LAB: same exported ABI, the variants and the
-    environment-to-option shim included."""
+    variants; libczk_hip_lab.so (tests / A/B tools) is the same source with -DCZK_LAB: every ABI symbol, plus the probe
+    (czk_lab_arith_probe, csrc/lab/arith_probe.hip -- not in include/czk.h), the variants and the environment-to-option shim included."""
     import os
     import subprocess
     import czk_amd
@@ -166,7 +166,8 @@ def test_product_library_has_no_environment_switches_and_no_lab_kernels():
     p, q = symbols(prod), symbols(lab)
     assert " U getenv" not in p and " U secure_getenv" not in p
     assert " U getenv" in q
-    lab_only = ("k_affine_round", "k_aff_build_first", "k_accumulate_u2p", "k_accumulate_u_lvl", "czk::k_accumulate<", "czk::k_reduce_level<")
+    lab_only = ("k_affine_round", "k_aff_build_first", "k_accumulate_u2p", "k_accumulate_u_lvl", "czk::k_accumulate<", "czk::k_reduce_level<",
+                "czk_lab_arith_probe")
     for k in lab_only:
         assert k not in p, f"{k} ships in the product library"
         assert k in q, f"{k} missing from the lab library"
@@ -174,6 +175,7 @@ def test_product_library_has_no_environment_switches_and_no_lab_kernels():
         assert k in p, k
     L = czk_amd.binding.lab_lib()
     assert [s for s in czk_amd.header_symbols() if not hasattr(L, s)] == []
+    assert "czk_lab_arith_probe" not in czk_amd.header_symbols() and hasattr(L, "czk_lab_arith_probe")
     assert czk_amd.lib().czk_build_is_lab() == 0 and L.czk_build_is_lab() == 1
     # no product source reads the environment either
     csrc = os.path.join(pkg, "csrc")

@@ -142,7 +142,7 @@ def emit():
     Rs = pow(2, 384, Q)          # R of field.h
     out = ["// te_constants.inc -- GENERATED by tools/gen_te_constants.py (derivation and self-check there); do not edit.",
            "// Twisted Edwards form -X^2 + Y^2 = 1 + D X^2 Y^2 of BLS12-377 G1 (E: y^2 = x^3 + 1):",
-           "//   w = (x + 1) / s,  X = f w / y,  Y = (w - 1) / (w + 1),   s^2 = 3, f^2 = -(A + 2) s^3, A = -3 / s, D = (A - 2) / (A + 2)",
+           "//   w = (x + 1) / s,  X = f w / y,  Y = (w - 1) / (w + 1),   s^2 = 3, f^2 = -(A + 2) s^3, A = -3 / s, D = -(A - 2) / (A + 2)",
            "// s = %d" % C["s"], "// f = %d" % C["f"], "// D = %d (a square: the unified law is exception-free on the prime-order subgroup, see the generator)" % C["D"]]
 
     def arr_u(name, v, comment):
