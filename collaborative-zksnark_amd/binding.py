@@ -68,6 +68,7 @@ def _load(path):
     L.czk_net_stats_reset.restype = None
     L.czk_sha256.restype = None
     L.czk_groth16_pvk_release.restype = None
+    L.czk_fixed_base_release.restype = None
     return L
 
 
@@ -140,6 +141,7 @@ class Context:
         `options`: {name: value} passed to czk_ctx_set_option before any work."""
         self._L = lab_lib() if lab else lib()
         self._lab = bool(lab)
+        self.device = int(device)
         self._h = C.c_void_p(0)
         rc = self._L.czk_ctx_create(C.byref(self._h), C.c_int(device), C.c_void_p(stream or 0))
         if rc:
@@ -550,6 +552,38 @@ class Context:
         self._ck(self._L.czk_fixed_base_points(self._h, C.c_int(group), _ptr(k), C.c_size_t(n), _ptr(out), C.c_int(mem)))
         return out
 
+    # ---- fixed-base MSM and the generator's helpers (czk_fixed_base_*, czk_fr_lagrange_coefficients) ----
+    def fixed_base(self, group: int, base, window: int = 0, n_hint: int = 0) -> "FixedBase":
+        """FixedBaseMSM::get_window_table for one finite affine base ((12|24,) uint64 Montgomery, host); window 0: chosen for n_hint scalars."""
+        if base is not None:
+            base = np.ascontiguousarray(base, np.uint64).reshape(12 if group == CZK_G1 else 24)
+        h = C.c_void_p(0)
+        self._ck(self._L.czk_fixed_base_create(self._h, C.c_int(group), _ptr(base), C.c_uint(window), C.c_size_t(n_hint), C.byref(h)))
+        return FixedBase(self, h, group)
+
+    def fixed_base_msm(self, fb: "FixedBase", k, out=None, n=None, scalar_form: int = CZK_SCALAR_CANONICAL, mem: int = CZK_MEM_HOST, out_inf=None):
+        """FixedBaseMSM::multi_scalar_mul + normalisation: returns (points (n, 12|24), infinity flags (n,)).  Host mode allocates both; in device
+        mode `k`, `out` and `out_inf` (may be None) are device pointers, `n` the count, and the same pair is returned."""
+        aw = 12 if fb.group == CZK_G1 else 24
+        if mem == CZK_MEM_HOST:
+            k = np.ascontiguousarray(k, np.uint64).reshape(-1, 4)
+            n = k.shape[0]
+            out = np.zeros((n, aw), dtype=np.uint64)
+            out_inf = np.zeros(n, dtype=np.uint8)
+        self._ck(self._L.czk_fixed_base_msm(self._h, fb._h, _ptr(k if n else None), C.c_size_t(n), C.c_int(scalar_form), _ptr(out if n else None),
+                                            _ptr(out_inf if n else None), C.c_int(mem)))
+        return out, out_inf
+
+    def fr_lagrange_coefficients(self, log_d: int, tau, n_out: int | None = None, out=None, mem: int = CZK_MEM_HOST):
+        """evaluate_all_lagrange_coefficients: L_j(tau) for j < n_out (default 2^log_d); tau: (4,) uint64 Montgomery, host."""
+        tau = np.ascontiguousarray(tau, np.uint64).reshape(4)
+        if n_out is None:
+            n_out = 1 << log_d
+        if mem == CZK_MEM_HOST:
+            out = np.zeros((n_out, 4), dtype=np.uint64)
+        self._ck(self._L.czk_fr_lagrange_coefficients(self._h, C.c_uint(log_d), _ptr(tau), _ptr(out if n_out else None), C.c_size_t(n_out), C.c_int(mem)))
+        return out
+
     # ---- pairing and Groth16 verification (czk_pairing*, czk_groth16_*) -----------------------------
     def pairing(self, g1, g2, g1_inf=None, g2_inf=None):
         """PairingEngine::pairing of n pairs: G1 (n, 12) and G2 (n, 24) affine Montgomery points -> (n, 72) Fq12 limbs."""
@@ -841,6 +875,30 @@ class PreparedVerifyingKey:
         if self._h:
             self.ctx._L.czk_groth16_pvk_release(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class FixedBase:
+    """czk_fixed_base: the window table of one base point, resident in HBM."""
+
+    def __init__(self, ctx: Context, handle, group: int):
+        self.ctx, self._h, self.group = ctx, handle, group
+
+    def layout(self):
+        """(window width, number of windows, table bytes) -- czk_fixed_base_layout."""
+        w, n, b = C.c_uint(0), C.c_uint(0), C.c_size_t(0)
+        self.ctx._L.czk_fixed_base_layout(self._h, C.byref(w), C.byref(n), C.byref(b))
+        return w.value, n.value, b.value
+
+    def release(self):
+        if self._h:
+            self.ctx._L.czk_fixed_base_release(self._h)
+            self._h = C.c_void_p(0)
 
     def __del__(self):
         try:

@@ -1460,6 +1460,15 @@ static int fixed_base_impl(czk_ctx* ctx, const u64* k_dev, size_t n, u64* out_de
     return CZK_OK;
 }
 
+// k_batch_to_affine for the other translation units (fixed_base.hip): n Jacobian points -> affine + infinity flags; scratch: n field elements
+void launch_batch_to_affine(hipStream_t st, int group, const u64* jac, size_t n, u64* scratch, u64* out_aff, uint8_t* out_inf) {
+    if (!n) return;
+    const unsigned CH = 32;
+    const dim3 grid((unsigned)(((n + CH - 1) / CH + 127) / 128));
+    if (group == CZK_G1) hipLaunchKernelGGL(k_batch_to_affine<Fq>, grid, dim3(128), 0, st, jac, n, CH, scratch, out_aff, out_inf);
+    else hipLaunchKernelGGL(k_batch_to_affine<Fq2>, grid, dim3(128), 0, st, jac, n, CH, scratch, out_aff, out_inf);
+}
+
 int fixed_base_points_device(czk_ctx* ctx, int group, const u64* k_dev, size_t n, u64* out_dev) {
     return group == CZK_G1 ? fixed_base_impl<Fq>(ctx, k_dev, n, out_dev) : fixed_base_impl<Fq2>(ctx, k_dev, n, out_dev);
 }

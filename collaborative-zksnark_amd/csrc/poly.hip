@@ -601,3 +601,54 @@ extern "C" int czk_fr_batch_inverse(czk_ctx* ctx, const uint64_t* v, size_t n, c
     CZK_HIP(ctx, hipGetLastError());
     return so.to_host(out, n * 32);
 }
+
+// EvaluationDomain::evaluate_all_lagrange_coefficients (poly/src/domain/radix2/mod.rs:119-185), composed from the entry points above:
+//   L_j(tau) = (Z(tau) / D) * w^j / (tau - w^j):  powers of w, tau minus them, batch_inversion_and_mul with Z(tau) / D, times the powers.
+// tau in the domain (:136-150): the coefficient of the element tau equals is one, every other is zero.
+extern "C" int czk_fr_lagrange_coefficients(czk_ctx* ctx, unsigned log_d, const uint64_t* tau, uint64_t* out, size_t n_out, int mem) {
+    if (!ctx || !tau || (n_out && !out)) return ctx ? set_err(ctx, CZK_ERR_ARG, "null lagrange_coefficients argument") : CZK_ERR_ARG;
+    if (!valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
+    DomainTables* d = nullptr;
+    CZK_TRY(get_domain(ctx, log_d, &d));
+    const u64 D = (u64)1 << log_d;
+    if (n_out > D) return set_err(ctx, CZK_ERR_ARG, "lagrange_coefficients: n_out exceeds the domain");
+    if (!n_out) return CZK_OK;
+    CZK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto limbs = [](const Fr& a, u64* p) {
+        for (int i = 0; i < 4; i++) p[i] = (u64)a.l[2 * i] | ((u64)a.l[2 * i + 1] << 32);
+    };
+    const Fr t = host_fr(tau), z = fp_sub(fp_pow_u64(t, D), Fr::one());
+    const size_t n = n_out;
+    Staged so{ctx};
+    CZK_TRY(so.to_device(mem == CZK_MEM_HOST ? nullptr : out, n * 32, mem));
+    if (z.is_zero()) {
+        CZK_HIP(ctx, hipMemsetAsync(so.dev, 0, n * 32, ctx->stream));
+        Fr w = Fr::one();
+        u64 one[4];
+        limbs(Fr::one(), one);
+        for (size_t i = 0; i < n; i++, w = fp_mul(w, d->group_gen))
+            if (w == t) {
+                CZK_HIP(ctx, hipMemcpyAsync((char*)so.dev + 32 * i, one, 32, hipMemcpyHostToDevice, ctx->stream));
+                break;
+            }
+        CZK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (`one` is a local)
+        return so.to_host(out, n * 32);
+    }
+    u64 g[4], tl[4], k[4], minus_one[4];
+    limbs(d->group_gen, g);
+    limbs(t, tl);
+    limbs(fp_mul(z, d->size_inv), k);
+    limbs(fp_neg(Fr::one()), minus_one);
+    DeviceBuf ws;
+    CZK_TRY(stage_take(ctx, 2 * n * 32, &ws));
+    u64 *pw = (u64*)ws.p, *den = pw + 4 * n;
+    const u64* terms[1] = {pw};
+    const size_t len[1] = {n}, lanes[1] = {1};
+    int rc = czk_fr_powers(ctx, g, nullptr, n, pw, CZK_MEM_DEVICE);
+    if (rc == CZK_OK) rc = czk_fr_lincomb(ctx, 1, terms, len, lanes, minus_one, tl, 1, 1, den, n);
+    if (rc == CZK_OK) rc = czk_fr_batch_inverse(ctx, den, n, k, (u64*)so.dev, CZK_MEM_DEVICE);
+    if (rc == CZK_OK) rc = czk_fr_vec_op(ctx, CZK_OP_MUL, (const u64*)so.dev, pw, (u64*)so.dev, n, CZK_MEM_DEVICE);
+    stage_give(ctx, ws);
+    CZK_TRY(rc);
+    return so.to_host(out, n * 32);
+}

@@ -500,6 +500,31 @@ int czk_jac_neg(czk_ctx* ctx, int group, const uint64_t* a_jac, uint64_t* out_ja
  * (SURVEY.md section 8d); also how tests obtain on-curve points with known discrete logs. */
 int czk_fixed_base_points(czk_ctx* ctx, int group, const uint64_t* k, size_t n, uint64_t* out, int mem);
 
+/* ---- fixed-base MSM: the generator's side (groth16/src/generator.rs:106-187) ---------------------- */
+/* FixedBaseMSM::get_window_table (algebra/ec/src/msm/fixed_base.rs:20-58) for ONE finite affine base (HOST memory, 12|24 u64 Montgomery; a base
+ * written as the point at infinity -- x = 0 with y = 0 or 1 -- is CZK_ERR_ARG), built on the context's GPU and kept in HBM until
+ * czk_fixed_base_release.  The base may be ANY finite point of the curve: like the reference's windowed_mul (:60-80) the multiplication makes no
+ * subgroup assumption.  window = 1..20 forces the width; window = 0 lets the library choose it for n_hint scalars (n_hint = 0: not known): the
+ * width with the fewest group additions, table build included, whose table stays below 1 GiB -- not the reference's get_mul_window_size
+ * (msm/mod.rs:10-13); the affine results do not depend on it.  Digits are signed: 2^(window - 1) entries per window.
+ * czk_fixed_base_layout (reporting only): *window, *windows = ceil(253 / window), plus one where window divides 253 (the signed form's carry can
+ * leave the top window there), *table_bytes = HBM the table occupies. */
+typedef struct czk_fixed_base czk_fixed_base;
+int czk_fixed_base_create(czk_ctx* ctx, int group, const uint64_t* base_aff, unsigned window, size_t n_hint, czk_fixed_base** out);
+void czk_fixed_base_release(czk_fixed_base* fb);
+int czk_fixed_base_layout(const czk_fixed_base* fb, unsigned* window, unsigned* windows, size_t* table_bytes);
+/* FixedBaseMSM::multi_scalar_mul (fixed_base.rs:82-95) + batch_normalization_into_affine (short_weierstrass_jacobian.rs:480-500):
+ * out_aff[i] = [k_i] base for i < n, one mixed addition per window.  scalars: n x 4 u64 in `scalar_form` (Montgomery scalars are decoded on the
+ * GPU); bits at and above 253 are ignored (fixed_base.rs:72).  out_aff: n x (12|24) u64 affine Montgomery; out_inf: n infinity bytes, may be
+ * NULL; k_i = 0 (mod the base's order) gives flag 1 and the coordinates (0, 1).  Buffers follow `mem`; with CZK_MEM_DEVICE the call only
+ * enqueues.  n = 0 is CZK_OK and writes nothing. */
+int czk_fixed_base_msm(czk_ctx* ctx, const czk_fixed_base* fb, const uint64_t* scalars, size_t n, int scalar_form, uint64_t* out_aff,
+                       uint8_t* out_inf, int mem);
+/* EvaluationDomain::evaluate_all_lagrange_coefficients (algebra/poly/src/domain/radix2/mod.rs:119-185) over the radix-2 domain of 2^log_d
+ * elements: out[j] = L_j(tau) for j < n_out <= 2^log_d (Montgomery Fr; `mem`).  tau: one Montgomery Fr, HOST memory.  Includes the branch for
+ * tau inside the domain (:136-150: the coefficient of the element tau equals is one, every other zero).  CZK_ERR_SIZE beyond 2^47. */
+int czk_fr_lagrange_coefficients(czk_ctx* ctx, unsigned log_d, const uint64_t* tau, uint64_t* out, size_t n_out, int mem);
+
 /* ---- Groth16 per-party local compute (callers of the two kernels) -------------------------------- */
 /* R1CStoQAP::witness_map minus its communication step (mpc-snarks/src/groth/r1cs_to_qap.rs:47-113), on `lanes`
  * Fr lanes of D = 2^log_d elements, all buffers lanes x D x 4 u64 in DEVICE memory:

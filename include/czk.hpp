@@ -10,6 +10,8 @@
 //   domain.divide_by_vanishing_poly_on_coset_in_place(&mut [F])              same name (domain/mod.rs:184-191)
 //   VariableBaseMSM::multi_scalar_mul(&[G], &[BigInt]) -> G::Projective      VariableBaseMSM::multi_scalar_mul(bases, scalars)
 //     (algebra/ec/src/msm/variable_base.rs:12-15)
+//   FixedBaseMSM::{get_window_table, multi_scalar_mul}                       FixedBaseMSM::get_window_table -> FixedBaseTable, multi_scalar_mul
+//     (algebra/ec/src/msm/fixed_base.rs:12-96)
 //   AffineCurve::multi_scalar_mul(&[Self], &[Fr]) -> Projective              G1Affine::multi_scalar_mul / G2Affine::multi_scalar_mul
 //     (algebra/ec/src/lib.rs:300-311)
 //   MpcField::{Public, Shared}, SpdzFieldShare{sh, mac}                      MpcField{shared, sh, mac}
@@ -407,6 +409,43 @@ struct VariableBaseMSM {
         G2Projective out;
         bases.ctx().check(czk_msm(bases.ctx().raw(), bases.raw(), scalars.empty() ? nullptr : scalars[0].l, scalars.size(), 1,
                                   CZK_SCALAR_CANONICAL, CZK_MEM_HOST, out.x.c0.l));
+        return out;
+    }
+};
+
+// algebra/ec/src/msm/fixed_base.rs:12-96 -- FixedBaseMSM as the Groth16 generator uses it (groth16/src/generator.rs:106-187): the window table
+// of ONE base is a handle in HBM (czk_fixed_base), multi_scalar_mul returns the points already normalised to affine limbs (12|24 u64 each,
+// Montgomery) with their infinity flags -- the generator's batch_normalization_into_affine.  window = 0: the library chooses it for n_hint scalars.
+template <int GROUP>
+class FixedBaseTable {
+  public:
+    FixedBaseTable(const Context& ctx, const uint64_t* base_xy, unsigned window = 0, size_t n_hint = 0) : ctx_(&ctx) {
+        ctx.check(czk_fixed_base_create(ctx.raw(), GROUP, base_xy, window, n_hint, &t_));
+    }
+    ~FixedBaseTable() { czk_fixed_base_release(t_); }
+    FixedBaseTable(const FixedBaseTable&) = delete;
+    FixedBaseTable& operator=(const FixedBaseTable&) = delete;
+    unsigned window() const { unsigned w = 0; czk_fixed_base_layout(t_, &w, nullptr, nullptr); return w; }
+    unsigned windows() const { unsigned n = 0; czk_fixed_base_layout(t_, nullptr, &n, nullptr); return n; }
+    size_t table_bytes() const { size_t b = 0; czk_fixed_base_layout(t_, nullptr, nullptr, &b); return b; }
+    czk_fixed_base* raw() const { return t_; }
+    const Context& ctx() const { return *ctx_; }
+
+  private:
+    const Context* ctx_;
+    czk_fixed_base* t_ = nullptr;
+};
+struct FixedBaseMSM {
+    template <int GROUP>
+    static FixedBaseTable<GROUP> get_window_table(const Context& ctx, unsigned window, const uint64_t* base_xy, size_t n_hint = 0) {
+        return FixedBaseTable<GROUP>(ctx, base_xy, window, n_hint);
+    }
+    template <int GROUP>
+    static std::vector<uint64_t> multi_scalar_mul(const FixedBaseTable<GROUP>& table, const std::vector<Fr>& v, std::vector<uint8_t>* infinity = nullptr) {
+        std::vector<uint64_t> out(v.size() * (GROUP == CZK_G1 ? 12 : 24));
+        if (infinity) infinity->assign(v.size(), 0);
+        table.ctx().check(czk_fixed_base_msm(table.ctx().raw(), table.raw(), v.empty() ? nullptr : v[0].l, v.size(), CZK_SCALAR_MONTGOMERY, out.data(),
+                                             infinity ? infinity->data() : nullptr, CZK_MEM_HOST));
         return out;
     }
 };

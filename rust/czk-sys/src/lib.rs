@@ -24,6 +24,10 @@ pub struct czk_r1cs_matrix {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct czk_fixed_base {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct czk_groth16_pvk {
     _private: [u8; 0],
 }
@@ -151,6 +155,11 @@ extern "C" {
     pub fn czk_jac_scalar_mul(ctx: *mut czk_ctx, group: c_int, a_jac: *const u64, k: *const u64, scalar_form: c_int, out_jac: *mut u64) -> c_int;
     pub fn czk_jac_neg(ctx: *mut czk_ctx, group: c_int, a_jac: *const u64, out_jac: *mut u64) -> c_int;
     pub fn czk_fixed_base_points(ctx: *mut czk_ctx, group: c_int, k: *const u64, n: usize, out: *mut u64, mem: c_int) -> c_int;
+    pub fn czk_fixed_base_create(ctx: *mut czk_ctx, group: c_int, base_aff: *const u64, window: c_uint, n_hint: usize, out: *mut *mut czk_fixed_base) -> c_int;
+    pub fn czk_fixed_base_release(fb: *mut czk_fixed_base);
+    pub fn czk_fixed_base_layout(fb: *const czk_fixed_base, window: *mut c_uint, windows: *mut c_uint, table_bytes: *mut usize) -> c_int;
+    pub fn czk_fixed_base_msm(ctx: *mut czk_ctx, fb: *const czk_fixed_base, scalars: *const u64, n: usize, scalar_form: c_int, out_aff: *mut u64, out_inf: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_fr_lagrange_coefficients(ctx: *mut czk_ctx, log_d: c_uint, tau: *const u64, out: *mut u64, n_out: usize, mem: c_int) -> c_int;
     pub fn czk_witness_map_pre(ctx: *mut czk_ctx, a: *mut u64, a_len: usize, b: *mut u64, b_len: usize, log_d: c_uint, lanes: usize) -> c_int;
     pub fn czk_witness_map_post(ctx: *mut czk_ctx, ab: *mut u64, c: *mut u64, c_len: usize, log_d: c_uint, lanes: usize) -> c_int;
     pub fn czk_pairing(ctx: *mut czk_ctx, g1: *const u64, g1_inf: *const u8, g2: *const u64, g2_inf: *const u8, n: usize, out: *mut u64, mem: c_int) -> c_int;

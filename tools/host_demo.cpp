@@ -708,6 +708,19 @@ int main(int argc, char** argv) {
     G1Projective acc2 = VariableBaseMSM::multi_scalar_mul(bases, ones_repr);
     ctx.check(czk_jac_to_affine(ctx.raw(), CZK_G1, acc2.x.l, 1, aff, &inf));
     REQUIRE(!inf && memcmp(aff, &pts[12 * n], 96) == 0);
+    // FixedBaseMSM over the generator (pts[0] = [1] G): the same points as czk_fixed_base_points gave for the same scalars; zero gives infinity
+    {
+        FixedBaseTable<CZK_G1> table = FixedBaseMSM::get_window_table<CZK_G1>(ctx, 0, pts.data(), n + 2);
+        const unsigned w = table.window();
+        REQUIRE(w >= 1 && w <= 20 && table.windows() == (253 + w - 1) / w + (253 % w == 0 ? 1 : 0) && table.table_bytes() > 0);
+        std::vector<uint64_t> raw(n + 2, 0);
+        for (size_t i = 0; i <= n; i++) raw[i] = k[4 * i];
+        std::vector<uint8_t> finf;
+        std::vector<uint64_t> got = FixedBaseMSM::multi_scalar_mul(table, fr_from_u64(ctx, raw), &finf);
+        REQUIRE(got.size() == 12 * (n + 2) && memcmp(got.data(), pts.data(), 96 * (n + 1)) == 0);
+        for (size_t i = 0; i <= n; i++) REQUIRE(!finf[i]);
+        REQUIRE(finf[n + 1] == 1);
+    }
     std::vector<MpcField> sc(n);
     for (size_t i = 0; i < n; i++) { sc[i].shared = true; sc[i].sh = ones[i]; sc[i].mac = x[i % 13]; }
     SpdzGroupShareG1 gs = SpdzGroupShareG1::multi_scale_pub_group(bases, sc);
