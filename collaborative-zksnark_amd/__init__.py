@@ -14,3 +14,4 @@ from . import binding  # noqa: F401
 from .build import build  # noqa: F401
 from . import parallel  # noqa: F401
 from . import keygen  # noqa: F401
+from . import keyio  # noqa: F401

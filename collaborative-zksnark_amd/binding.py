@@ -20,6 +20,10 @@ CZK_MEM_SCALAR_HOST = 256    # czk_fr_vec_scale: device vectors, host scalar
 CZK_MEM_SAME_SCALARS = 512   # czk_msm_async: the scalars of the previous czk_msm_async call (its digit sort may be reused)
 CZK_MEM_CHECK_SUBGROUP = 128  # czk_bases_register: verify [r] P == infinity; a failing base keeps the handle on the XYZZ kernels
 CZK_SCALAR_CANONICAL, CZK_SCALAR_MONTGOMERY = 0, 1
+CZK_POINTS_COMPRESSED, CZK_POINTS_CHECKED = 1, 2   # czk_points_deserialize flags
+# czk_point_status
+CZK_POINT_OK, CZK_POINT_BAD_FLAGS, CZK_POINT_NOT_CANONICAL, CZK_POINT_NO_POINT, CZK_POINT_NOT_ON_CURVE, CZK_POINT_NOT_IN_SUBGROUP = range(6)
+POINT_STATUS_NAMES = ("OK", "BAD_FLAGS", "NOT_CANONICAL", "NO_POINT", "NOT_ON_CURVE", "NOT_IN_SUBGROUP")
 CZK_G1, CZK_G2 = 1, 2
 CZK_OP_ADD, CZK_OP_SUB, CZK_OP_MUL = 0, 1, 2
 CZK_NET_RCCL, CZK_NET_SHM, CZK_NET_IPC = 1, 2, 3
@@ -583,6 +587,56 @@ class Context:
             out = np.zeros((n_out, 4), dtype=np.uint64)
         self._ck(self._L.czk_fr_lagrange_coefficients(self._h, C.c_uint(log_d), _ptr(tau), _ptr(out if n_out else None), C.c_size_t(n_out), C.c_int(mem)))
         return out
+
+    # ---- square roots and the reference's point encoding (czk_fq_sqrt, czk_points_*) ---------------------
+    def fq_sqrt(self, a, ext: int = 1, out=None, out_exists=None, n=None, mem: int = CZK_MEM_HOST):
+        """Square roots in Fq (ext = 1, (n, 6)) or Fq2 (ext = 2, (n, 12)), Montgomery limbs: returns (roots, exists flags); the root is the one with
+        y <= -y, zero where none exists.  Host mode allocates both; in device mode `a`, `out`, `out_exists` are device pointers and `n` the count."""
+        fw = 6 * ext
+        if mem == CZK_MEM_HOST:
+            a = np.ascontiguousarray(a, np.uint64).reshape(-1, fw)
+            n = a.shape[0]
+            out = np.zeros((n, fw), dtype=np.uint64)
+            out_exists = np.zeros(n, dtype=np.uint8)
+        self._ck(self._L.czk_fq_sqrt(self._h, C.c_int(ext), _ptr(a if n else None), C.c_size_t(n), _ptr(out if n else None),
+                                     _ptr(out_exists if n else None), C.c_int(mem)))
+        return out, out_exists
+
+    def points_serialize(self, group: int, pts, inf=None, compressed: bool = True, n=None, out=None, mem: int = CZK_MEM_HOST):
+        """GroupAffine::serialize / serialize_uncompressed of n affine Montgomery points ((n, 12|24)) with optional infinity flags: host mode returns
+        the bytes as a uint8 array; in device mode `pts`, `inf` (may be None) and `out` are device pointers, `n` the count, and `out` is returned."""
+        aw = 12 if group == CZK_G1 else 24
+        if mem == CZK_MEM_HOST:
+            pts = np.ascontiguousarray(pts, np.uint64).reshape(-1, aw)
+            n = pts.shape[0]
+            inf = None if inf is None else np.ascontiguousarray(inf, np.uint8).reshape(n)
+            out = np.zeros(n * aw * (4 if compressed else 8), dtype=np.uint8)
+        self._ck(self._L.czk_points_serialize(self._h, C.c_int(group), _ptr(pts if n else None), _ptr(inf if n else None), C.c_size_t(n),
+                                              C.c_int(1 if compressed else 0), _ptr(out if n else None), C.c_int(mem)))
+        return out
+
+    def points_deserialize(self, group: int, data, n=None, compressed: bool = True, checked: bool = True, out=None, out_inf=None, out_status=None,
+                           count: bool = True, mem: int = CZK_MEM_HOST):
+        """GroupAffine::deserialize (compressed, checked), deserialize_uncompressed (checked), deserialize_unchecked (neither) of n points: returns
+        (points (n, 12|24), infinity flags, czk_point_status bytes, number of failing points, first failing index or n).  Host mode takes bytes or a
+        uint8 array and allocates the outputs; in device mode `data`, `out`, `out_inf`, `out_status` (may be None) are device pointers, and
+        count=False returns None for the two counts and only enqueues."""
+        aw = 12 if group == CZK_G1 else 24
+        size = aw * (4 if compressed else 8)
+        if mem == CZK_MEM_HOST:
+            data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, np.uint8)
+            if data.size % size:
+                raise ValueError(f"{data.size} bytes are not a whole number of {size}-byte points")
+            n = data.size // size
+            out = np.zeros((n, aw), dtype=np.uint64)
+            out_inf = np.zeros(n, dtype=np.uint8)
+            out_status = np.zeros(n, dtype=np.uint8)
+        flags = (CZK_POINTS_COMPRESSED if compressed else 0) | (CZK_POINTS_CHECKED if checked else 0)
+        bad, first = C.c_size_t(0), C.c_size_t(n)
+        self._ck(self._L.czk_points_deserialize(self._h, C.c_int(group), _ptr(data if n else None), C.c_size_t(n), C.c_int(flags), _ptr(out if n else None),
+                                                _ptr(out_inf if n else None), _ptr(out_status if n else None), C.byref(bad) if count else None,
+                                                C.byref(first) if count else None, C.c_int(mem)))
+        return out, out_inf, out_status, (bad.value if count else None), (first.value if count else None)
 
     # ---- pairing and Groth16 verification (czk_pairing*, czk_groth16_*) -----------------------------
     def pairing(self, g1, g2, g1_inf=None, g2_inf=None):

@@ -402,6 +402,7 @@ extern "C" void czk_ctx_destroy(czk_ctx* ctx) {
     for (auto& b : ctx->stage_pool) (void)hipFree(b.p);
     ctx->stage_pool.clear();
     if (ctx->share_tab.p) (void)hipFree(ctx->share_tab.p);
+    if (ctx->sqrt_tab.p) (void)hipFree(ctx->sqrt_tab.p);
     msm_pipeline_destroy(ctx);
     xfer_destroy(ctx);
     prof_resolve(ctx);

@@ -45,6 +45,25 @@ struct GT<Fq2> {
     static constexpr int AW = 24, JW = 36, FW = 12, XW = 48;
 };
 
+// COEFF_B of y^2 = x^3 + b, Montgomery form (k_subgroup_check in msm.hip, the point decoder in point_codec.hip)
+template <class F>
+struct CurveB;
+template <>
+struct CurveB<Fq> {   // COEFF_B = 1 (curves/bls12_377/src/curves/g1.rs:23)
+    static CZK_HD Fq get() { return Fq::one(); }
+};
+template <>
+struct CurveB<Fq2> {   // COEFF_B = (0, 1552...4906) (curves/bls12_377/src/curves/g2.rs:28-34), c1 in Montgomery form
+    static CZK_HD Fq2 get() {
+        Fq2 b = Fq2::zero();
+        constexpr u32 m[12] = {0x66666685u, 0x80722666u, 0x899999a9u, 0x8df55926u, 0xd64f34cfu, 0x7fe4561au,
+                               0xb6e4f01bu, 0xb95da6d8u, 0xfc142743u, 0x4b747cccu, 0x70f49f43u, 0x0039c3fau};
+#pragma unroll
+        for (int i = 0; i < 12; i++) b.c1.l[i] = m[i];
+        return b;
+    }
+};
+
 }  // namespace czk
 
 namespace czk {
@@ -167,6 +186,7 @@ struct czk_ctx {
     czk::DeviceBuf ntt_scratch;   // one lane-batch for the out-of-place NTT passes
     czk::DeviceBuf poly_scratch;  // segment sums of czk_poly_div_linear (poly.hip)
     czk::DeviceBuf share_tab;     // size_inv * w^(-jk) table of czk_fr_gsz_open (share.hip)
+    czk::DeviceBuf sqrt_tab;      // 2-adic discrete-log tables of the Fq square root (point_codec.hip), built on first use
     int num_cu = 256;
     size_t lds_per_block = 64 * 1024;   // hipDeviceProp_t::sharedMemPerBlock (gfx950: 160 KiB)
 };

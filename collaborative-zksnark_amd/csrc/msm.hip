@@ -638,23 +638,7 @@ static int te_table_from_sw(czk_ctx* ctx, const u64* sw, const uint8_t* inf, siz
 // for this check (czk_bases_check_subgroup, or CZK_MEM_CHECK_SUBGROUP at registration: a failing base keeps the handle on the XYZZ kernels).
 // One thread per point: on-curve test (y^2 = x^3 + b), then [r] P by MSB-first double-and-add with the complete Jacobian formulas of curve.h.
 // ------------------------------------------------------------------------------------------------
-template <class F>
-struct CurveB;
-template <>
-struct CurveB<Fq> {   // COEFF_B = 1 (curves/bls12_377/src/curves/g1.rs:23)
-    static CZK_HD Fq get() { return Fq::one(); }
-};
-template <>
-struct CurveB<Fq2> {   // COEFF_B = (0, 1552...4906) (curves/bls12_377/src/curves/g2.rs:28-34), c1 in Montgomery form
-    static CZK_HD Fq2 get() {
-        Fq2 b = Fq2::zero();
-        constexpr u32 m[12] = {0x66666685u, 0x80722666u, 0x899999a9u, 0x8df55926u, 0xd64f34cfu, 0x7fe4561au,
-                               0xb6e4f01bu, 0xb95da6d8u, 0xfc142743u, 0x4b747cccu, 0x70f49f43u, 0x0039c3fau};
-#pragma unroll
-        for (int i = 0; i < 12; i++) b.c1.l[i] = m[i];
-        return b;
-    }
-};
+// (the curve constants CurveB<F> are in czk_internal.h: point_codec.hip's decoder uses them too)
 template <class F>
 __global__ __launch_bounds__(128) void k_subgroup_check(const u64* aff, const uint8_t* inf, size_t n, u32* bad) {
     // r = 0x12ab655e9a2ca55660b44d1e5c37b00159aa76fed00000010a11800000000001, 253 bits (curves/bls12_377/src/fields/fr.rs MODULUS)

@@ -537,6 +537,49 @@ int czk_fr_lagrange_coefficients(czk_ctx* ctx, unsigned log_d, const uint64_t* t
 int czk_witness_map_pre(czk_ctx* ctx, uint64_t* a, size_t a_len, uint64_t* b, size_t b_len, unsigned log_d, size_t lanes);
 int czk_witness_map_post(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes);
 
+/* ---- square roots and the reference's byte format of curve points -------------------------------- */
+/* SquareRootField::sqrt over Fq (ext = 1: n x 6 u64) or Fq2 (ext = 2: n x 12 u64), Montgomery form, one thread per element.
+ * out_exists[i] = 1 and out[i] = a root of a[i], or out_exists[i] = 0 and out[i] = 0 when a[i] has none.  The root of 0 is 0 and exists.
+ * ROOT CHOICE: of the two roots, the y with y <= -y in the reference's order (Fq by into_repr(); Fq2 by c1, then c0:
+ * quadratic_extension.rs:412-418).  This DIFFERS from SquareRootField::sqrt, which returns whichever root its Tonelli-Shanks loop lands on
+ * (ff/src/fields/arithmetic.rs:259-320); no serialization path observes that choice (get_point_from_x normalises it,
+ * short_weierstrass_jacobian.rs:108-118).  Fq2 elements with c1 = 0 and c0 a non-residue of Fq have the root (0, sqrt(c0 / -5)) here; the
+ * reference's Fq2 sqrt answers None for them (quadratic_extension.rs:363-365).  Buffers follow `mem`; with CZK_MEM_DEVICE the call only enqueues. */
+int czk_fq_sqrt(czk_ctx* ctx, int ext, const uint64_t* a, size_t n, uint64_t* out, uint8_t* out_exists, int mem);
+
+/* CanonicalSerialize / CanonicalDeserialize for GroupAffine (short_weierstrass_jacobian.rs:792-895): n affine Montgomery points + infinity
+ * bytes <-> the reference's bytes.  Per point: G1 48 (compressed) / 96 bytes, G2 96 / 192 bytes; each Fq is the 48 little-endian bytes of
+ * into_repr(), an Fq2 is c0 then c1; SWFlags (serialize/src/flags.rs:110-135) sit in the top two bits of the point's LAST byte: bit 7 =
+ * PositiveY (y > -y; compressed finite points only), bit 6 = Infinity.  Byte buffers in DEVICE memory must be 8-byte aligned (CZK_ERR_ARG).
+ *
+ * czk_points_serialize: serialize (compressed != 0) or serialize_uncompressed.  inf: n bytes, NULL = none infinite; a point flagged infinite
+ *   is written as GroupAffine::zero() whatever its coordinates hold: x = 0 with the infinity bit, or (0, 1) with the bit on y.
+ * czk_points_deserialize: flags = CZK_POINTS_COMPRESSED and / or CZK_POINTS_CHECKED --
+ *     COMPRESSED | CHECKED = deserialize, CHECKED = deserialize_uncompressed, 0 = deserialize_unchecked, COMPRESSED alone = get_point_from_x
+ *     without the subgroup test (the reference has no such entry point).
+ *   Per point, in this order: both flag bits set -> CZK_POINT_BAD_FLAGS; a coordinate >= q (a flag bit on any Fq but the last included) ->
+ *   CZK_POINT_NOT_CANONICAL; the infinity bit -> infinity, written as flag 1 with the coordinates (0, 1) (uncompressed input too, where the
+ *   reference keeps the coordinates it read); compressed: y^2 = x^3 + b has no root -> CZK_POINT_NO_POINT, else y by the PositiveY bit;
+ *   uncompressed: (x, y) as read, bit 7 ignored.  CHECKED then tests [r] P == 0 -> CZK_POINT_NOT_IN_SUBGROUP, and for uncompressed input
+ *   first y^2 == x^3 + b -> CZK_POINT_NOT_ON_CURVE.  That on-curve test is STRICTER than the reference, whose deserialize_uncompressed
+ *   assumes it (is_in_correct_subgroup_assuming_on_curve).  Without CHECKED uncompressed points get no test at all, as in the reference.
+ *   A failing point gets flag 0 and zero coordinates; the others are unaffected (the reference fails the whole read with InvalidData).
+ *   out_status: n bytes of czk_point_status, follows `mem`, may be NULL.  out_bad / out_first_bad: HOST size_t, each may be NULL: the number
+ *   of failing points and the smallest failing index (n when none fails).  With CZK_MEM_DEVICE and both NULL the call only enqueues.
+ * n = 0 is CZK_OK. */
+typedef enum { CZK_POINTS_COMPRESSED = 1, CZK_POINTS_CHECKED = 2 } czk_points_flags;
+typedef enum {
+    CZK_POINT_OK = 0,
+    CZK_POINT_BAD_FLAGS = 1,
+    CZK_POINT_NOT_CANONICAL = 2,
+    CZK_POINT_NO_POINT = 3,
+    CZK_POINT_NOT_ON_CURVE = 4,
+    CZK_POINT_NOT_IN_SUBGROUP = 5
+} czk_point_status;
+int czk_points_serialize(czk_ctx* ctx, int group, const uint64_t* pts, const uint8_t* inf, size_t n, int compressed, uint8_t* out_bytes, int mem);
+int czk_points_deserialize(czk_ctx* ctx, int group, const uint8_t* bytes, size_t n, int flags, uint64_t* out_pts, uint8_t* out_inf,
+                           uint8_t* out_status, size_t* out_bad, size_t* out_first_bad, int mem);
+
 /* ---- pairing and Groth16 verification ------------------------------------------------------------ */
 /* The reference's pairing engine Bls12::<Parameters> (X = 0x8508c00000000001, TwistType::D; curves/bls12_377/src/curves/mod.rs:16-19,
  * algebra/ec/src/models/bls12/mod.rs) on the GPU, one product of pairings per thread.  Points are affine Montgomery (G1: 12 u64, G2: 24 u64)

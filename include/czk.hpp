@@ -714,4 +714,74 @@ inline bool verify_proof(const PreparedVerifyingKey& pvk, const Proof& proof, co
     return ok != 0;
 }
 
+// ---- CanonicalSerialize / CanonicalDeserialize of the affine points (czk_points_serialize / czk_points_deserialize) -----------------------
+//   GroupAffine::{serialize, serialize_uncompressed}                (short_weierstrass_jacobian.rs:792-828)   serialize(ctx, points, compressed)
+//   GroupAffine::{deserialize, deserialize_uncompressed, _unchecked} (:858-895)                               deserialize / deserialize_uncompressed / deserialize_unchecked
+//   Proof's derived impls (groth16/src/data_structures.rs:11-18)                                              serialize(ctx, proof) / deserialize_proof
+// A Vec's u64 length prefix is the caller's (serialize/src/lib.rs:220-229): these take and return the items only.  A bad element panics with
+// InvalidData naming its index, as the reference's read fails as a whole.
+template <class Point> struct PointCodec;
+template <> struct PointCodec<G1AffinePoint> { static constexpr int group = CZK_G1; static constexpr size_t words = 12; };
+template <> struct PointCodec<G2AffinePoint> { static constexpr int group = CZK_G2; static constexpr size_t words = 24; };
+
+template <class Point>
+inline std::vector<uint8_t> serialize(const Context& ctx, const std::vector<Point>& pts, bool compressed = true) {
+    constexpr size_t W = PointCodec<Point>::words;
+    std::vector<uint64_t> xy(pts.size() * W);
+    std::vector<uint8_t> inf(pts.size()), out(pts.size() * W * (compressed ? 4 : 8));
+    for (size_t i = 0; i < pts.size(); i++) {
+        std::memcpy(&xy[W * i], &pts[i].x, W * 8);
+        inf[i] = pts[i].infinity;
+    }
+    ctx.check(czk_points_serialize(ctx.raw(), PointCodec<Point>::group, xy.data(), inf.data(), pts.size(), compressed ? 1 : 0, out.data(), CZK_MEM_HOST));
+    return out;
+}
+template <class Point>
+inline std::vector<Point> deserialize_points(const Context& ctx, const uint8_t* bytes, size_t len, int flags) {
+    constexpr size_t W = PointCodec<Point>::words;
+    const size_t size = W * ((flags & CZK_POINTS_COMPRESSED) ? 4 : 8), n = len / size;
+    if (len % size) throw Panic(CZK_ERR_ARG, "InvalidData: the buffer is not a whole number of points");
+    std::vector<uint64_t> xy(n * W);
+    std::vector<uint8_t> inf(n), status(n);
+    size_t bad = 0, first = n;
+    ctx.check(czk_points_deserialize(ctx.raw(), PointCodec<Point>::group, bytes, n, flags, xy.data(), inf.data(), status.data(), &bad, &first, CZK_MEM_HOST));
+    if (bad) throw Panic(CZK_ERR_CHECK, "InvalidData: point " + std::to_string(first) + " (czk_point_status " + std::to_string(status[first]) + ")");
+    std::vector<Point> out(n);
+    for (size_t i = 0; i < n; i++) {
+        std::memcpy(&out[i].x, &xy[W * i], W * 8);
+        out[i].infinity = inf[i] != 0;
+    }
+    return out;
+}
+template <class Point>
+inline std::vector<Point> deserialize(const Context& ctx, const std::vector<uint8_t>& bytes) {
+    return deserialize_points<Point>(ctx, bytes.data(), bytes.size(), CZK_POINTS_COMPRESSED | CZK_POINTS_CHECKED);
+}
+template <class Point>
+inline std::vector<Point> deserialize_uncompressed(const Context& ctx, const std::vector<uint8_t>& bytes) {
+    return deserialize_points<Point>(ctx, bytes.data(), bytes.size(), CZK_POINTS_CHECKED);
+}
+template <class Point>
+inline std::vector<Point> deserialize_unchecked(const Context& ctx, const std::vector<uint8_t>& bytes) {
+    return deserialize_points<Point>(ctx, bytes.data(), bytes.size(), 0);
+}
+// Proof = a | b | c: 192 bytes compressed
+inline std::vector<uint8_t> serialize(const Context& ctx, const Proof& proof, bool compressed = true) {
+    std::vector<uint8_t> out = serialize<G1AffinePoint>(ctx, {proof.a}, compressed), b = serialize<G2AffinePoint>(ctx, {proof.b}, compressed),
+                         c = serialize<G1AffinePoint>(ctx, {proof.c}, compressed);
+    out.insert(out.end(), b.begin(), b.end());
+    out.insert(out.end(), c.begin(), c.end());
+    return out;
+}
+inline Proof deserialize_proof(const Context& ctx, const std::vector<uint8_t>& bytes, bool compressed = true, bool checked = true) {
+    const size_t g1 = compressed ? 48 : 96;
+    if (bytes.size() != 4 * g1) throw Panic(CZK_ERR_ARG, "InvalidData: a Proof is " + std::to_string(4 * g1) + " bytes");
+    const int flags = (compressed ? CZK_POINTS_COMPRESSED : 0) | (checked ? CZK_POINTS_CHECKED : 0);
+    Proof p;
+    p.a = deserialize_points<G1AffinePoint>(ctx, bytes.data(), g1, flags)[0];
+    p.b = deserialize_points<G2AffinePoint>(ctx, bytes.data() + g1, 2 * g1, flags)[0];
+    p.c = deserialize_points<G1AffinePoint>(ctx, bytes.data() + 3 * g1, g1, flags)[0];
+    return p;
+}
+
 }  // namespace czk

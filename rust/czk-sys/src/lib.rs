@@ -61,6 +61,14 @@ pub const CZK_OP_MUL: c_int = 2; // czk_binop
 pub const CZK_NET_RCCL: c_int = 1; // czk_net_transport
 pub const CZK_NET_SHM: c_int = 2; // czk_net_transport
 pub const CZK_NET_IPC: c_int = 3; // czk_net_transport
+pub const CZK_POINTS_COMPRESSED: c_int = 1; // czk_points_flags
+pub const CZK_POINTS_CHECKED: c_int = 2; // czk_points_flags
+pub const CZK_POINT_OK: c_int = 0; // czk_point_status
+pub const CZK_POINT_BAD_FLAGS: c_int = 1; // czk_point_status
+pub const CZK_POINT_NOT_CANONICAL: c_int = 2; // czk_point_status
+pub const CZK_POINT_NO_POINT: c_int = 3; // czk_point_status
+pub const CZK_POINT_NOT_ON_CURVE: c_int = 4; // czk_point_status
+pub const CZK_POINT_NOT_IN_SUBGROUP: c_int = 5; // czk_point_status
 pub const CZK_NET_UNIQUE_ID_BYTES: c_int = 128; // #define
 pub const CZK_OPEN_COMMIT: c_int = 1; // #define
 
@@ -162,6 +170,9 @@ extern "C" {
     pub fn czk_fr_lagrange_coefficients(ctx: *mut czk_ctx, log_d: c_uint, tau: *const u64, out: *mut u64, n_out: usize, mem: c_int) -> c_int;
     pub fn czk_witness_map_pre(ctx: *mut czk_ctx, a: *mut u64, a_len: usize, b: *mut u64, b_len: usize, log_d: c_uint, lanes: usize) -> c_int;
     pub fn czk_witness_map_post(ctx: *mut czk_ctx, ab: *mut u64, c: *mut u64, c_len: usize, log_d: c_uint, lanes: usize) -> c_int;
+    pub fn czk_fq_sqrt(ctx: *mut czk_ctx, ext: c_int, a: *const u64, n: usize, out: *mut u64, out_exists: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_points_serialize(ctx: *mut czk_ctx, group: c_int, pts: *const u64, inf: *const u8, n: usize, compressed: c_int, out_bytes: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_points_deserialize(ctx: *mut czk_ctx, group: c_int, bytes: *const u8, n: usize, flags: c_int, out_pts: *mut u64, out_inf: *mut u8, out_status: *mut u8, out_bad: *mut usize, out_first_bad: *mut usize, mem: c_int) -> c_int;
     pub fn czk_pairing(ctx: *mut czk_ctx, g1: *const u64, g1_inf: *const u8, g2: *const u64, g2_inf: *const u8, n: usize, out: *mut u64, mem: c_int) -> c_int;
     pub fn czk_pairing_product(ctx: *mut czk_ctx, g1: *const u64, g1_inf: *const u8, g2: *const u64, g2_inf: *const u8, offsets: *const usize, k: usize, out: *mut u64, out_is_one: *mut u8, mem: c_int) -> c_int;
     pub fn czk_groth16_pvk_create(ctx: *mut czk_ctx, alpha_g1: *const u64, beta_g2: *const u64, gamma_g2: *const u64, delta_g2: *const u64, gamma_abc_g1: *const u64, gamma_abc_inf: *const u8, n_gamma_abc: usize, out: *mut *mut czk_groth16_pvk) -> c_int;

@@ -798,6 +798,32 @@ int main(int argc, char** argv) {
         REQUIRE(!linf && !rinf && memcmp(laff, raff, 96) == 0);
     }
 
+    // a Proof leaves as the 192 bytes of its derived CanonicalSerialize impl and comes back (checked: subgroup test included)
+    {
+        const uint64_t k1[8] = {11, 0, 0, 0, 13, 0, 0, 0}, k2[4] = {12, 0, 0, 0};
+        Proof pr;
+        uint64_t g1[24], g2[24];
+        ctx.check(czk_fixed_base_points(ctx.raw(), CZK_G1, k1, 2, g1, CZK_MEM_HOST));
+        ctx.check(czk_fixed_base_points(ctx.raw(), CZK_G2, k2, 1, g2, CZK_MEM_HOST));
+        memcpy(&pr.a.x, g1, 96);
+        memcpy(&pr.c.x, g1 + 12, 96);
+        memcpy(&pr.b.x, g2, 192);
+        std::vector<uint8_t> wire = serialize(ctx, pr);
+        REQUIRE(wire.size() == 192);
+        Proof back = deserialize_proof(ctx, wire);
+        REQUIRE(!back.a.infinity && !back.b.infinity && !back.c.infinity);
+        REQUIRE(memcmp(&back.a.x, &pr.a.x, 96) == 0 && memcmp(&back.b.x, &pr.b.x, 192) == 0 && memcmp(&back.c.x, &pr.c.x, 96) == 0);
+        REQUIRE(serialize(ctx, pr, false).size() == 384);
+        wire[3] ^= 1;                                              // another x: no point, or one outside the subgroup
+        bool threw = false;
+        try {
+            deserialize_proof(ctx, wire);
+        } catch (const Panic& p) {
+            threw = p.code == CZK_ERR_CHECK;
+        }
+        REQUIRE(threw);
+    }
+
     // ConstraintMatrix::evaluate: rows {z0 + 3 z2, (empty), z1} on z = (2, 5, 7)
     {
         std::vector<Fr> c = fr_from_u64(ctx, {1, 3, 2, 5, 7, 23});
