@@ -133,6 +133,40 @@ LAB_ARITH_PROBE_OPS = {
 LAB_ARITH_PROBE_OPS.update({f"fru_sub<{1 << lg},{u}>": (100 + 2 * lg + (u - 1), 18, 9) for lg in range(1, 9) for u in (1, 2)})
 
 
+def _sat_probe_ops():
+    """enum czk_lab_sat_fn of csrc/lab/arith_probe.h: the saturated field.h / tower.h / curve.h.  `name` is the function compiled with the
+    Montgomery multiply inlined (op 200 + 2 fn), `name@noinline` the same function compiled with -DCZK_NOINLINE_MUL (op 200 + 2 fn + 1);
+    the Fq6 / Fq12 functions exist in the second form only."""
+    fns = {}
+    for base, f, w in ((0, "fr", 8), (10, "fq", 12)):
+        for i, (nm, k) in enumerate((("add", 2), ("sub", 2), ("dbl", 1), ("neg", 1), ("reduce", 1), ("mul", 2), ("sqr", 1), ("into_repr", 1),
+                                     ("from_repr", 1), ("inv", 1))):
+            fns[f"{f}_{nm}"] = (base + i, k * w, w)
+    fns["fq_mul_by_nonresidue"] = (20, 12, 12)
+    for i, (nm, iw) in enumerate((("add", 48), ("sub", 48), ("dbl", 24), ("neg", 24), ("mul", 48), ("sqr", 24), ("inv", 24), ("mul_by_u", 24),
+                                  ("mul_fq", 36), ("conj", 24))):
+        fns[f"fq2_{nm}"] = (21 + i, iw, 24)
+    for base, g, w in ((31, "g1", 12), (41, "g2", 24)):
+        for i, (nm, iw, ow) in enumerate((("jac_double", 3, 3), ("jac_add_mixed", 5, 3), ("jac_add", 6, 3), ("jac_to_affine", 3, 2),
+                                          ("xyzz_double_affine", 2, 4), ("xyzz_double", 4, 4), ("xyzz_add_mixed", 6, 4), ("xyzz_acc_mixed", 6, 4),
+                                          ("xyzz_add", 8, 4), ("xyzz_to_jac", 4, 3))):
+            fns[f"{g}_{nm}"] = (base + i, iw * w + (nm == "jac_add_mixed"), ow * w + (nm == "jac_to_affine"))
+    tower = {}
+    for i, (nm, iw) in enumerate((("add", 144), ("sub", 144), ("neg", 72), ("mul_by_v", 72), ("mul", 144), ("mul_by_01", 120), ("mul_by_1", 96),
+                                  ("inv", 72), ("frobenius_1", 72), ("frobenius_2", 72))):
+        tower[f"fq6_{nm}"] = (51 + i, iw, 72)
+    for i, (nm, iw) in enumerate((("mul", 288), ("sqr", 144), ("conj", 144), ("inv", 144), ("mul_by_034", 216), ("frobenius_1", 144),
+                                  ("frobenius_2", 144), ("cyclotomic_square", 144), ("load_strided_1", 144), ("store_strided_1", 144),
+                                  ("load_strided_n", 144), ("store_strided_n", 144))):
+        tower[f"fq12_{nm}"] = (61 + i, iw, 144)
+    ops = {nm: (200 + 2 * fn, iw, ow) for nm, (fn, iw, ow) in fns.items()}
+    ops.update({nm + "@noinline": (200 + 2 * fn + 1, iw, ow) for nm, (fn, iw, ow) in {**fns, **tower}.items()})
+    return ops
+
+
+LAB_ARITH_PROBE_OPS.update(_sat_probe_ops())
+
+
 class Context:
     """czk_ctx: one GPU + one HIP stream = one MPC party.
 
@@ -167,8 +201,8 @@ class Context:
 
     def lab_arith_probe(self, op: str, items):
         """czk_lab_arith_probe (csrc/lab/arith_probe.h, lab library only): runs the function named `op` (a key of LAB_ARITH_PROBE_OPS)
-        of the unsaturated arithmetic headers once per row of `items` -- raw u32 limbs exactly as given -- and returns the raw result
-        rows.  Raises unless the context was opened with lab=True: the product library does not carry the probe."""
+        of the unsaturated arithmetic headers, or of the saturated field.h / tower.h / curve.h, once per row of `items` -- raw u32 limbs
+        exactly as given -- and returns the raw result rows.  Raises unless the context was opened with lab=True: the product library does not carry the probe."""
         if not self._lab:
             raise RuntimeError("lab_arith_probe needs Context(lab=True): libczk_hip.so does not export czk_lab_arith_probe")
         code, iw, ow = LAB_ARITH_PROBE_OPS[op]

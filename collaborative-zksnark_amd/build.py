@@ -6,9 +6,12 @@
                      batched-affine rounds, safegcd inversion, interleaved multiply-add chains, Karatsuba Fq2; the lane-pair G2 accumulate
                      kernel, the saturated accumulate / reduction kernels) and the CZK_* environment switches of the measurement tools,
                      which it translates into options.  Every ABI symbol, plus the probe: csrc/lab/arith_probe.hip (LAB_SOURCES) exports
-                     czk_lab_arith_probe, which runs one function of the unsaturated arithmetic headers on raw limbs for
-                     tests/test_lazy_arith.py.  Loaded by tests through Context(lab=True) and by tools through CZK_LIB_PATH; never by
-                     the provers.
+                     czk_lab_arith_probe, which runs one function on raw limbs: of the unsaturated arithmetic headers for
+                     tests/test_lazy_arith.py, and of the saturated field.h / tower.h / curve.h (csrc/lab/sat_probe.h) for
+                     tests/test_sat_arith.py.  The saturated probes are compiled in both forms field.h is built in: with the Montgomery
+                     multiply inlined in arith_probe.hip, and with -DCZK_NOINLINE_MUL (the form of pairing.hip, the only one the Fq6 / Fq12
+                     tower has) in csrc/lab/sat_probe.hip.  Loaded by tests through Context(lab=True) and by tools through CZK_LIB_PATH;
+                     never by the provers.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container as well as on the GPU box.
 """
@@ -30,10 +33,10 @@ SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_
            ("msm_acc_g2.hip", []), ("msm_red_g2.hip", []), ("msm_heavy_g2.hip", []), ("poly.hip", []), ("share.hip", []), ("net.hip", ["-DCZK_NOINLINE_MUL"]),
            ("pairing.hip", ["-DCZK_NOINLINE_MUL"]), ("fixed_base.hip", []), ("point_codec.hip", ["-DCZK_NOINLINE_MUL"])]
 # lab library only: never compiled into, nor linked with, the product library
-LAB_SOURCES = [(os.path.join("lab", "arith_probe.hip"), [])]
+LAB_SOURCES = [(os.path.join("lab", "arith_probe.hip"), []), (os.path.join("lab", "sat_probe.hip"), ["-DCZK_NOINLINE_MUL"])]
 HEADERS = ["field.h", "curve.h", "czk_internal.h", "msm_acc.h", "fq2p.h", "fq2pu.h", "fqu.h", "fru.h", "fru_constants.inc", "ntt_pass.h", "te.h", "te_constants.inc", "tower.h", "pairing_constants.inc",
            os.path.join("..", "..", "include", "czk.h")]
-LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h", "arith_probe.h")]
+LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h", "arith_probe.h", "sat_probe.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-pass-failed", "-I" + CSRC]
 # parallel hipcc jobs: CZK_BUILD_JOBS, else the MAX_JOBS a build host sets (a container's os.cpu_count() is the whole machine's), else all cores

@@ -897,7 +897,7 @@ CZK_HD Fp<P> fp_pow_u64(const Fp<P>& a, u64 e) {
     return fp_pow(a, &e, 1);
 }
 
-// Inverse by Fermat: a^(p-2).  Value-identical to macros.rs:367-421 (the inverse is unique); used only
+// Inverse by Fermat: a^(p-2), so fp_inv(0) == 0 (and f_inv(0) == 0 up the tower).  Value-identical to macros.rs:367-421 (the inverse is unique); used only
 // for O(1)-per-call work (domain constants, one Z^-1 per MSM result), never in a hot loop.
 template <class P>
 CZK_HD Fp<P> fp_inv(const Fp<P>& a) {

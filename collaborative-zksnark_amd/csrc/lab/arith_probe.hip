@@ -1,12 +1,16 @@
 // arith_probe.hip -- LAB BUILD ONLY (build.py LAB_SOURCES): one small kernel per function of the unsaturated arithmetic headers, fed raw
 // limbs from memory and storing raw limbs back.  See arith_probe.h for the item layouts and tests/test_lazy_arith.py for the user.
 // The headers are compiled here in their own translation unit, with the hot kernels' flags (the Montgomery multiply inlined).
+// Ops from CZK_PROBE_SAT_BASE up are the saturated field.h / curve.h (sat_probe.h): the inlined form is compiled here, the
+// -DCZK_NOINLINE_MUL form (and the tower) in sat_probe.hip, which the switch below dispatches to.
 #include "arith_probe.h"
 
+#include "curve.h"
 #include "czk_internal.h"
 #include "fq2pu.h"
 #include "fru.h"
 #include "te.h"
+#include "tower.h"
 
 namespace czk {
 namespace {
@@ -183,6 +187,9 @@ int probe(czk_ctx* ctx, const uint32_t* in, size_t iw, uint32_t* out, size_t ow,
     return so.to_host(out, n * ow * 4);
 }
 
+// the saturated arithmetic, compiled in this translation unit's form: the Montgomery multiply inlined
+#include "sat_probe.h"
+
 }  // namespace
 }  // namespace czk
 
@@ -247,7 +254,13 @@ extern "C" int czk_lab_arith_probe(czk_ctx* ctx, int op, const uint32_t* in, siz
     case CZK_PROBE_FRU_SUB_BASE + 2 * LG + 1: RUN(PFruSub<(1 << LG), 2>);
         SUBS(1) SUBS(2) SUBS(3) SUBS(4) SUBS(5) SUBS(6) SUBS(7) SUBS(8)
 #undef SUBS
-    default: return set_err(ctx, CZK_ERR_ARG, "arith_probe: unknown op");
+    default: break;
     }
 #undef RUN
+    if (op >= CZK_PROBE_SAT_BASE && op < CZK_PROBE_SAT_BASE + 2 * CZK_SAT_FN_COUNT) {
+        const int fn = (op - CZK_PROBE_SAT_BASE) / 2;
+        if ((op - CZK_PROBE_SAT_BASE) % 2) return sat_probe_noinline(ctx, fn, in, in_words_per_item, out, out_words_per_item, n, mem);
+        return sat_probe_dispatch(ctx, fn, in, in_words_per_item, out, out_words_per_item, n, mem);
+    }
+    return set_err(ctx, CZK_ERR_ARG, "arith_probe: unknown op");
 }

@@ -95,6 +95,50 @@ def test_products_of_pairings(ctx):
     assert one[0] == 1 and np.array_equal(got[0], ONE_LIMBS)
 
 
+@pytest.fixture(scope="module")
+def pair_pool(ctx):
+    """eight pairs (P_i, Q_i), the last four the first four with P negated, and the GPU's single pairings of them: values the first test
+    pins to the model"""
+    pts1 = [P.g1_mul(i * 7919 + 5) for i in range(4)]
+    pts2 = [P.g2_mul(i * 104729 + 13) for i in range(4)]
+    pts1 += [P.ec_neg(P.F1, p) for p in pts1]
+    pts2 += pts2
+    single = ctx.pairing(_g1(pts1)[0], _g2(pts2)[0])
+    return pts1, pts2, [P.fq12_from_limbs(row) for row in single]
+
+
+@pytest.mark.parametrize("k", [63, 64, 65, 130])
+def test_products_of_pairings_across_the_wave_boundary(ctx, pair_pool, k):
+    """The final exponentiation parks three Fq12 per thread in a workspace laid out SoA with stride k: k just below, at and above one
+    wave, and above two.  Products of 0 to 3 pairs, infinity flags scattered on either side, every value and every is-one flag exact."""
+    pts1, pts2, single = pair_pool
+    offs, g1, g2, i1, i2, want = [0], [], [], [], [], []
+    for j in range(k):
+        size = (j + j // 4) % 4
+        idx = [(3 * j + 4 * t) % 8 for t in range(size)]          # t and t + 1 pick (i, i + 4): e(P, Q) e(-P, Q) == 1
+        acc = P.FQ12_ONE
+        for t, i in enumerate(idx):
+            inf1, inf2 = (5 * j + t) % 7 == 0, (3 * j + 2 * t) % 11 == 0
+            g1.append(P.INF if (5 * j + t) % 14 == 0 else pts1[i])   # an infinity flag with and without the point's limbs beside it
+            g2.append(P.INF if (3 * j + 2 * t) % 22 == 0 else pts2[i])
+            i1.append(int(inf1))
+            i2.append(int(inf2))
+            if not (inf1 or inf2):
+                acc = P.fq12_mul(acc, single[i])
+        offs.append(len(g1))
+        want.append(acc)
+    a1, a2 = _g1(g1)[0], _g2(g2)[0]
+    got, one = ctx.pairing_product(a1, a2, offs, np.array(i1, dtype=np.uint8), np.array(i2, dtype=np.uint8))
+    sizes = np.diff(offs)
+    assert set(sizes) == {0, 1, 2, 3} and 0 < sum(i1) < len(i1) and 0 < sum(i2) < len(i2)
+    ones = [w == P.FQ12_ONE for w in want]
+    assert any(o and s == 2 and not (i1[a] or i2[a] or i1[a + 1] or i2[a + 1]) for o, s, a in zip(ones, sizes, offs)), "no e(P, Q) e(-P, Q) product"
+    assert any(not o for o in ones)
+    for j in range(k):
+        assert np.array_equal(got[j], np.array(P.fq12_to_limbs(want[j]), dtype=np.uint64)), (k, j)
+    assert list(one) == [int(o) for o in ones]
+
+
 # ------------------------------------------------------------------------------------------------------------------- Groth16
 def _proof(N, parties, scheme):
     """A Groth16 proof of the squaring circuit under a real key (as tests/test_verify.py builds it), opened: returns (key, A, B, C affine limbs, out)."""
