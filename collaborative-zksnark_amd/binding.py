@@ -73,6 +73,7 @@ def _load(path):
     L.czk_sha256.restype = None
     L.czk_groth16_pvk_release.restype = None
     L.czk_fixed_base_release.restype = None
+    L.czk_kzg10_vk_release.restype = None
     return L
 
 
@@ -672,6 +673,105 @@ class Context:
                                                 C.byref(first) if count else None, C.c_int(mem)))
         return out, out_inf, out_status, (bad.value if count else None), (first.value if count else None)
 
+    # ---- elementwise group arithmetic on arrays of points (czk_points_add / _mul / _sum) -------------------
+    def points_add(self, group: int, a, b, a_inf=None, b_inf=None, negate_b: bool = False, n=None, out=None, out_inf=None, mem: int = CZK_MEM_HOST):
+        """out[i] = a[i] + b[i] (a[i] - b[i] with negate_b) over affine Montgomery points ((n, 12|24)) with optional infinity flags, every exceptional
+        case included: returns (points, infinity flags).  Host mode allocates both; in device mode every buffer is a device pointer and `n` the count."""
+        aw = 12 if group == CZK_G1 else 24
+        if mem == CZK_MEM_HOST:
+            a = np.ascontiguousarray(a, np.uint64).reshape(-1, aw)
+            n = a.shape[0]
+            b = np.ascontiguousarray(b, np.uint64).reshape(n, aw)
+            a_inf = None if a_inf is None else np.ascontiguousarray(a_inf, np.uint8).reshape(n)
+            b_inf = None if b_inf is None else np.ascontiguousarray(b_inf, np.uint8).reshape(n)
+            out = np.zeros((n, aw), dtype=np.uint64)
+            out_inf = np.zeros(n, dtype=np.uint8)
+        z = lambda x: x if n else None
+        self._ck(self._L.czk_points_add(self._h, C.c_int(group), _ptr(z(a)), _ptr(z(a_inf)), _ptr(z(b)), _ptr(z(b_inf)), C.c_size_t(n),
+                                        C.c_int(1 if negate_b else 0), _ptr(z(out)), _ptr(z(out_inf)), C.c_int(mem)))
+        return out, out_inf
+
+    def points_mul(self, group: int, pts, k, inf=None, stride: int = 1, scalar_form: int = CZK_SCALAR_CANONICAL, n=None, out=None, out_inf=None,
+                   mem: int = CZK_MEM_HOST):
+        """out[i] = [k_i] P_i, ProjectiveCurve::mul over all 256 bits of the scalar: returns (points, infinity flags).  stride=1: `pts` holds one point
+        per scalar; stride=0: ONE point (and flag) for every scalar.  k: (n, 4) uint64 in `scalar_form`.  Device mode as for points_add."""
+        aw = 12 if group == CZK_G1 else 24
+        if mem == CZK_MEM_HOST:
+            k = np.ascontiguousarray(k, np.uint64).reshape(-1, 4)
+            n = k.shape[0]
+            pts = np.ascontiguousarray(pts, np.uint64).reshape(n if stride else 1, aw)
+            inf = None if inf is None else np.ascontiguousarray(inf, np.uint8).reshape(n if stride else 1)
+            out = np.zeros((n, aw), dtype=np.uint64)
+            out_inf = np.zeros(n, dtype=np.uint8)
+        z = lambda x: x if n else None
+        self._ck(self._L.czk_points_mul(self._h, C.c_int(group), _ptr(z(pts)), _ptr(z(inf)), C.c_size_t(stride), _ptr(z(k)), C.c_size_t(n),
+                                        C.c_int(scalar_form), _ptr(z(out)), _ptr(z(out_inf)), C.c_int(mem)))
+        return out, out_inf
+
+    def points_sum(self, group: int, pts, offsets, inf=None, out=None, out_inf=None, mem: int = CZK_MEM_HOST):
+        """Segmented sums: out[j] = sum of pts[offsets[j] .. offsets[j+1]) for the k = len(offsets) - 1 segments (an empty one is infinity): returns
+        (points (k, 12|24), infinity flags).  offsets are host values in either mode.  Device mode as for points_add."""
+        aw = 12 if group == CZK_G1 else 24
+        offs = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        k = max(offs.size - 1, 0)
+        if mem == CZK_MEM_HOST:
+            pts = np.ascontiguousarray(pts, np.uint64).reshape(-1, aw)
+            if k and int(offs[-1]) > pts.shape[0]:
+                raise ValueError("offsets reach beyond the points")
+            inf = None if inf is None else np.ascontiguousarray(inf, np.uint8).reshape(pts.shape[0])
+            out = np.zeros((k, aw), dtype=np.uint64)
+            out_inf = np.zeros(k, dtype=np.uint8)
+        z = lambda x: x if k else None
+        self._ck(self._L.czk_points_sum(self._h, C.c_int(group), _ptr(z(pts)), _ptr(z(inf)), _ptr(z(offs)), C.c_size_t(k), _ptr(z(out)), _ptr(z(out_inf)),
+                                        C.c_int(mem)))
+        return out, out_inf
+
+    # ---- KZG10 verification (czk_kzg10_*) -----------------------------------------------------------
+    def kzg10_vk(self, g, gamma_g, h, beta_h) -> "Kzg10VerifierKey":
+        """VerifierKey (g, gamma_g: (12,), h, beta_h: (24,) uint64 affine Montgomery, finite) in HBM: a Kzg10VerifierKey handle."""
+        g, gamma_g = (np.ascontiguousarray(x, np.uint64).reshape(12) for x in (g, gamma_g))
+        h, beta_h = (np.ascontiguousarray(x, np.uint64).reshape(24) for x in (h, beta_h))
+        hd = C.c_void_p()
+        self._ck(self._L.czk_kzg10_vk_create(self._h, _ptr(g), _ptr(gamma_g), _ptr(h), _ptr(beta_h), C.byref(hd)))
+        return Kzg10VerifierKey(self, hd, g.copy(), gamma_g.copy(), h.copy(), beta_h.copy())
+
+    @staticmethod
+    def _kzg_openings(comm, points, values, w, comm_inf, w_inf, random_v):
+        comm = np.ascontiguousarray(comm, np.uint64).reshape(-1, 12)
+        k = comm.shape[0]
+        points, values = (np.ascontiguousarray(x, np.uint64).reshape(k, 4) for x in (points, values))
+        w = np.ascontiguousarray(w, np.uint64).reshape(k, 12)
+        comm_inf = None if comm_inf is None else np.ascontiguousarray(comm_inf, np.uint8).reshape(k)
+        w_inf = None if w_inf is None else np.ascontiguousarray(w_inf, np.uint8).reshape(k)
+        random_v = None if random_v is None else np.ascontiguousarray(random_v, np.uint64).reshape(k, 4)
+        return k, comm, comm_inf, points, values, w, w_inf, random_v
+
+    def kzg10_check(self, vk: "Kzg10VerifierKey", comm, points, values, w, comm_inf=None, w_inf=None, random_v=None):
+        """KZG10::check of k openings: comm, w (k, 12) with optional flags; points, values, random_v (None = not hiding) (k, 4) Montgomery Fr ->
+        (k,) bool."""
+        k, comm, comm_inf, points, values, w, w_inf, random_v = self._kzg_openings(comm, points, values, w, comm_inf, w_inf, random_v)
+        ok = np.zeros(k, dtype=np.uint8)
+        z = lambda x: x if k else None
+        self._ck(self._L.czk_kzg10_check(self._h, vk._h, _ptr(z(comm)), _ptr(z(comm_inf)), _ptr(z(points)), _ptr(z(values)), _ptr(z(w)), _ptr(z(w_inf)),
+                                         _ptr(z(random_v)), C.c_size_t(k), _ptr(z(ok)), C.c_int(CZK_MEM_HOST)))
+        return ok.astype(bool)
+
+    def kzg10_batch_check(self, vk: "Kzg10VerifierKey", comm, points, values, w, randomizers, offsets, comm_inf=None, w_inf=None, random_v=None):
+        """KZG10::batch_check of b = len(offsets) - 1 batches, batch j = openings [offsets[j], offsets[j+1]) of the arrays of kzg10_check;
+        randomizers: (k, 4) CANONICAL uint64, one per opening -> (b,) bool."""
+        k, comm, comm_inf, points, values, w, w_inf, random_v = self._kzg_openings(comm, points, values, w, comm_inf, w_inf, random_v)
+        offs = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        b = max(offs.size - 1, 0)
+        if b and int(offs[-1]) != k:
+            raise ValueError("offsets must end at the number of openings")
+        r = np.ascontiguousarray(randomizers, np.uint64).reshape(k, 4)
+        ok = np.zeros(b, dtype=np.uint8)
+        z = lambda x: x if k else None
+        self._ck(self._L.czk_kzg10_batch_check(self._h, vk._h, _ptr(z(comm)), _ptr(z(comm_inf)), _ptr(z(points)), _ptr(z(values)), _ptr(z(w)),
+                                               _ptr(z(w_inf)), _ptr(z(random_v)), _ptr(z(r)), _ptr(offs if b else None), C.c_size_t(b),
+                                               _ptr(ok if b else None), C.c_int(CZK_MEM_HOST)))
+        return ok.astype(bool)
+
     # ---- pairing and Groth16 verification (czk_pairing*, czk_groth16_*) -----------------------------
     def pairing(self, g1, g2, g1_inf=None, g2_inf=None):
         """PairingEngine::pairing of n pairs: G1 (n, 12) and G2 (n, 24) affine Montgomery points -> (n, 72) Fq12 limbs."""
@@ -962,6 +1062,25 @@ class PreparedVerifyingKey:
     def release(self):
         if self._h:
             self.ctx._L.czk_groth16_pvk_release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class Kzg10VerifierKey:
+    """czk_kzg10_vk: a KZG10 verifier key (g, gamma_g, h, beta_h) resident in HBM; the four points are kept as numpy arrays too."""
+
+    def __init__(self, ctx: Context, handle, g, gamma_g, h, beta_h):
+        self.ctx, self._h = ctx, handle
+        self.g, self.gamma_g, self.h, self.beta_h = g, gamma_g, h, beta_h
+
+    def release(self):
+        if self._h:
+            self.ctx._L.czk_kzg10_vk_release(self._h)
             self._h = None
 
     def __del__(self):

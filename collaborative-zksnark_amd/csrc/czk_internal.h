@@ -369,6 +369,16 @@ int ctx_wait_mark(czk_ctx* ctx, uint64_t id);
 void msm_pipeline_destroy(czk_ctx* ctx);
 int fixed_base_points_device(czk_ctx* ctx, int group, const u64* k_dev, size_t n, u64* out_dev);
 void launch_batch_to_affine(hipStream_t st, int group, const u64* jac, size_t n, u64* scratch, u64* out_aff, uint8_t* out_inf);   // Montgomery's trick, 32 points per inversion
+// implemented in point_ops.hip: czk_points_add / _mul / _sum over DEVICE buffers (flags may be null = none infinite; a stride of 0 repeats one point;
+// offs_host: k + 1 host offsets, already validated).  Each only enqueues on the context's stream.
+int points_add_device(czk_ctx* ctx, int group, const u64* a, const uint8_t* a_inf, size_t a_stride, const u64* b, const uint8_t* b_inf, size_t b_stride,
+                      size_t n, int negate_b, u64* out, uint8_t* out_inf);
+int points_mul_device(czk_ctx* ctx, int group, const u64* pts, const uint8_t* inf, size_t stride, const u64* scalars, size_t n, int scalar_form, u64* out,
+                      uint8_t* out_inf);
+int points_sum_device(czk_ctx* ctx, int group, const u64* pts, const uint8_t* inf, const size_t* offs_host, size_t k, u64* out, uint8_t* out_inf);
+// implemented in pairing.hip: is_one[j] = the product of pairings over pairs [offs_host[j], offs_host[j + 1]) is one (device buffers; blocking)
+int pairing_is_one_device(czk_ctx* ctx, const u64* g1, const uint8_t* g1_inf, const u64* g2, const uint8_t* g2_inf, const size_t* offs_host, size_t k,
+                          uint8_t* is_one);
 void launch_reduce_level_g1(hipStream_t st, const u64* P, const u64* E, size_t n_in, unsigned L, unsigned scale_dbl, u64* Po, u64* Eo, size_t n_out,
                             unsigned lanes);
 // (G2: `ub` = buckets and level arrays in u-form, reduced on fq2pu.h's unsaturated lane pairs)

@@ -279,6 +279,13 @@ static int pairing_products_device(czk_ctx* ctx, CallBufs& cb, const u64* g1, co
     return CZK_OK;
 }
 
+// the KZG10 verifier's entry (kzg.hip)
+int pairing_is_one_device(czk_ctx* ctx, const u64* g1, const uint8_t* g1_inf, const u64* g2, const uint8_t* g2_inf, const size_t* offs_host, size_t k,
+                          uint8_t* is_one) {
+    CallBufs cb(ctx);
+    return pairing_products_device(ctx, cb, g1, g1_inf, g2, g2_inf, offs_host, k, nullptr, is_one);
+}
+
 static int pairing_products(czk_ctx* ctx, const uint64_t* g1, const uint8_t* g1_inf, const uint64_t* g2, const uint8_t* g2_inf,
                             const size_t* offs, size_t k, uint64_t* out, uint8_t* out_is_one, int mem) {
     const size_t n = offs[k];

@@ -22,6 +22,8 @@ VK_FIELDS = (("alpha_g1", 1, False), ("beta_g2", 2, False), ("gamma_g2", 2, Fals
 PK_FIELDS = VK_FIELDS + (("beta_g1", 1, False), ("delta_g1", 1, False), ("a_query", 1, True), ("b_g1_query", 1, True), ("b_g2_query", 2, True),
                          ("h_query", 1, True), ("l_query", 1, True))
 PROOF_FIELDS = (("a", 1, False), ("b", 2, False), ("c", 1, False))
+# KZG10's VerifierKey (poly-commit/src/kzg10/data_structures.rs:192-286): the prepared G2 points are not serialized
+KZG10_VK_FIELDS = (("g", 1, False), ("gamma_g", 1, False), ("h", 2, False), ("beta_h", 2, False))
 
 
 def point_size(group: int, compressed: bool = True) -> int:
@@ -162,3 +164,30 @@ def groth16_proof_to_bytes(ctx, proof, compressed: bool = True) -> bytes:
 
 def groth16_proof_from_bytes(ctx, data, compressed: bool = True, checked: bool = True) -> dict:
     return _from_bytes(ctx, PROOF_FIELDS, data, compressed, checked, True, "Proof")
+
+
+def kzg10_vk_size(compressed: bool = True) -> int:
+    """bytes of a serialized KZG10 VerifierKey: 48 + 48 + 96 + 96 = 288 compressed, 576 uncompressed"""
+    return _layout(KZG10_VK_FIELDS, {}, compressed)[1]
+
+
+def kzg10_vk_layout(compressed: bool = True) -> dict:
+    """{field: (byte offset, number of points = 1, group)} of a serialized KZG10 VerifierKey, plus "size" """
+    out, size = _layout(KZG10_VK_FIELDS, {}, compressed)
+    out["size"] = size
+    return out
+
+
+def kzg10_vk_to_bytes(ctx, vk, compressed: bool = True) -> bytes:
+    """VerifierKey::serialize (compressed) / serialize_uncompressed = serialize_unchecked (data_structures.rs:192-219): g | gamma_g | h | beta_h.
+    vk: a Kzg10VerifierKey, or a dict with those four points as affine Montgomery limbs."""
+    if not isinstance(vk, dict):
+        vk = {name: getattr(vk, name) for name, _, _ in KZG10_VK_FIELDS}
+    return _to_bytes(ctx, KZG10_VK_FIELDS, vk, compressed)
+
+
+def kzg10_vk_from_bytes(ctx, data, compressed: bool = True, checked: bool = True):
+    """VerifierKey::deserialize (compressed, checked), deserialize_uncompressed (checked) or deserialize_unchecked (neither) (:229-286): a
+    Kzg10VerifierKey on the context's GPU.  Raises ValueError on truncated or over-long input and on the first invalid point, before the key is made."""
+    obj = _from_bytes(ctx, KZG10_VK_FIELDS, data, compressed, checked, True, "kzg10::VerifierKey")
+    return ctx.kzg10_vk(obj["g"], obj["gamma_g"], obj["h"], obj["beta_h"])

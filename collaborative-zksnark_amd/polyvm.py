@@ -291,6 +291,17 @@ class GpuBackend(Backend):
 
     M = 1   # CZK_MEM_DEVICE
 
+    def verifier_key(self):
+        """(g, gamma_g, h, beta_h) of this backend's SRS -- KZG10's VerifierKey (poly-commit/src/kzg10/data_structures.rs:173-190) as affine
+        Montgomery limbs, made on first use: g = powers_of_g[0], gamma_g = powers_of_gamma_g[0], h = the G2 generator, beta_h = [tau] h."""
+        if getattr(self, "_vk", None) is None:
+            czk, ctx = self.czk, self.ctx
+            limbs = lambda v: [(v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(4)]
+            g = ctx.fixed_base_points(czk.CZK_G1, np.array([limbs(1)], dtype=np.uint64))[0]
+            hs = ctx.fixed_base_points(czk.CZK_G2, np.array([limbs(1), limbs(self.tau % R_MOD)], dtype=np.uint64))
+            self._vk = (g, np.array(self.bases_gamma_host()[0], dtype=np.uint64), hs[0], hs[1])
+        return self._vk
+
     def prepare(self, sizes):
         """czk_bases_prepare for the commitment lengths a prover will use: the narrower secondary table sets short polynomials run on are built at SRS
         load instead of inside the first proof's czk_msm_async (which would drain the MSM pipeline mid-proof to build them)."""

@@ -613,6 +613,50 @@ void czk_groth16_pvk_release(czk_groth16_pvk* pvk);
 int czk_groth16_verify(czk_ctx* ctx, const czk_groth16_pvk* pvk, const uint64_t* a, const uint64_t* b, const uint64_t* c, const uint8_t* inf,
                        const uint64_t* public_inputs, size_t m, size_t k, uint8_t* out_ok, int mem);
 
+/* ---- elementwise group arithmetic on arrays of points --------------------------------------------- */
+/* The O(n) group steps of a verifier, on the GPU (the host calls czk_jac_add / czk_jac_scalar_mul above take one point at a time).  Points are
+ * affine Montgomery (G1: 12 u64, G2: 24 u64) plus infinity bytes (input flags NULL = none infinite); results are normalised to affine with one
+ * shared batch inversion per call (batch_normalization_into_affine, short_weierstrass_jacobian.rs:480-500): infinity is flag 1 with the
+ * coordinates (0, 1); out_inf may be NULL.  NO subgroup assumption: every point of the curve is a valid input -- (0, 1) with flag 0 is the
+ * order-3 point, not infinity.  Buffers follow `mem`; with CZK_MEM_DEVICE a call only enqueues.  n = 0 (k = 0) is CZK_OK and writes nothing.
+ *
+ * czk_points_add: out[i] = a[i] + b[i], or a[i] - b[i] with negate_b != 0 -- add_assign_mixed with its whole case analysis (:570-638): either side
+ *   infinite, a = b (doubling), a = -b (infinity).  out may alias a or b.
+ * czk_points_mul: out[i] = [k_i] P_i, ProjectiveCurve::mul (algebra/ec/src/lib.rs:215-230): double-and-add over ALL 256 bits of the canonical
+ *   scalar, most significant first (a scalar >= r is not reduced first: the points need not have order r).  scalars: n x 4 u64 in `scalar_form`
+ *   (Montgomery scalars are decoded on the GPU).  pts_stride = 1: n points and flags; pts_stride = 0: ONE point (and flag) for every scalar.
+ * czk_points_sum: k segmented sums, out[j] = sum of pts[offsets[j] .. offsets[j+1]); an empty segment is infinity.  offsets (k + 1 entries,
+ *   offsets[0] == 0, non-decreasing) are HOST memory whatever `mem` says and are read before the call returns.  One wave per segment, the lanes'
+ *   partial sums combined by the complete addition (:666-728): equal and opposite partial sums are handled. */
+int czk_points_add(czk_ctx* ctx, int group, const uint64_t* a, const uint8_t* a_inf, const uint64_t* b, const uint8_t* b_inf, size_t n, int negate_b,
+                   uint64_t* out, uint8_t* out_inf, int mem);
+int czk_points_mul(czk_ctx* ctx, int group, const uint64_t* pts, const uint8_t* inf, size_t pts_stride, const uint64_t* scalars, size_t n,
+                   int scalar_form, uint64_t* out, uint8_t* out_inf, int mem);
+int czk_points_sum(czk_ctx* ctx, int group, const uint64_t* pts, const uint8_t* inf, const size_t* offsets, size_t k, uint64_t* out, uint8_t* out_inf,
+                   int mem);
+
+/* ---- KZG10 verification (poly-commit/src/kzg10/mod.rs:295-371) ------------------------------------- */
+/* VerifierKey (poly-commit/src/kzg10/data_structures.rs:173-190) into device memory of the context's GPU: g, gamma_g (G1, 12 u64 each), h, beta_h
+ * (G2, 24 u64 each), HOST memory, finite points.  The handle stays valid until czk_kzg10_vk_release and may be used by any context of the same
+ * device. */
+typedef struct czk_kzg10_vk czk_kzg10_vk;
+int czk_kzg10_vk_create(czk_ctx* ctx, const uint64_t* g, const uint64_t* gamma_g, const uint64_t* h, const uint64_t* beta_h, czk_kzg10_vk** out);
+void czk_kzg10_vk_release(czk_kzg10_vk* vk);
+/* KZG10::check (mod.rs:295-314) over k independent openings: out_ok[i] = 1 iff e(C_i - [v_i] g - [rv_i] gamma_g, h) * e(-W_i, beta_h - [z_i] h)
+ * is one -- the same decision as the reference's lhs == rhs (the final exponentiation is a homomorphism), one Miller loop over two pairs and one
+ * final exponentiation per opening.  comm, w: k x 12 u64 with flags (NULL = none infinite); points, values: k x 4 u64 Montgomery Fr; random_v:
+ * k x 4 Montgomery Fr, NULL = no opening is hiding (Proof::random_v = None; a zero entry decides the same as None).  As in the reference no point
+ * gets a subgroup or on-curve check; a pair with infinity on either side is skipped (z = beta, the zero polynomial).  Buffers follow `mem`; blocks. */
+int czk_kzg10_check(czk_ctx* ctx, const czk_kzg10_vk* vk, const uint64_t* comm, const uint8_t* comm_inf, const uint64_t* points, const uint64_t* values,
+                    const uint64_t* w, const uint8_t* w_inf, const uint64_t* random_v, size_t k, uint8_t* out_ok, int mem);
+/* KZG10::batch_check (mod.rs:318-371) over b batches: batch j covers openings [offsets[j], offsets[j+1]) of the same per-opening arrays, and
+ * out_ok[j] = 1 iff e(-total_w, beta_h) * e(total_c, h) is one, with total_c = sum r_i (C_i + [z_i] W_i) - [sum r_i v_i] g - [sum r_i rv_i] gamma_g
+ * and total_w = sum r_i W_i.  randomizers: one per opening, n x 4 u64 CANONICAL, supplied by the caller (the reference uses 1 for a batch's first
+ * opening and 128-bit random values after it).  offsets (b + 1 entries, offsets[0] == 0, non-decreasing): HOST memory.  An empty batch is ok. */
+int czk_kzg10_batch_check(czk_ctx* ctx, const czk_kzg10_vk* vk, const uint64_t* comm, const uint8_t* comm_inf, const uint64_t* points,
+                          const uint64_t* values, const uint64_t* w, const uint8_t* w_inf, const uint64_t* random_v, const uint64_t* randomizers,
+                          const size_t* offsets, size_t b, uint8_t* out_ok, int mem);
+
 /* ---- measurement hooks --------------------------------------------------------------------------- */
 /* When enabled, the library brackets its kernel launches with HIP events on the context's stream (the stream the
  * kernels run on) and accumulates per-kernel elapsed time.  Names: "msm_accumulate_g1", "msm_accumulate_g2",

@@ -14,6 +14,8 @@
 //     (algebra/ec/src/msm/fixed_base.rs:12-96)
 //   AffineCurve::multi_scalar_mul(&[Self], &[Fr]) -> Projective              G1Affine::multi_scalar_mul / G2Affine::multi_scalar_mul
 //     (algebra/ec/src/lib.rs:300-311)
+//   KZG10::{check, batch_check}, VerifierKey                                 KZG10::check / batch_check, KZG10::VerifierKey
+//     (poly-commit/src/kzg10/mod.rs:295-371, data_structures.rs:173-190)
 //   MpcField::{Public, Shared}, SpdzFieldShare{sh, mac}                      MpcField{shared, sh, mac}
 //     (mpc-algebra/src/wire/field.rs:27-30, share/spdz.rs:50-53)
 //   GroupShare::multi_scale_pub_group(bases, &[share]) (SPDZ)                SpdzGroupShare::multi_scale_pub_group
@@ -506,9 +508,82 @@ struct SpdzGroupShareG1 {
     }
 };
 
+// affine points as the verifiers take them (the pairing, Groth16 and KZG10 checks below): Montgomery coordinates + the infinity flag
+struct G1AffinePoint { Fq x, y; bool infinity = false; };
+struct G2AffinePoint { Fq2 x, y; bool infinity = false; };
+
 // poly-commit/src/kzg10/mod.rs:141-193 -- KZG10::commit for a single prover: MSM over powers_of_g plus, when hiding, an
 // MSM over powers_of_gamma_g joined with add_assign_mixed (Marlin / Plonk reach the MSM kernel through this).
+// KZG10::check / batch_check (:295-371) and the VerifierKey (data_structures.rs:173-190) are the verifier's side, on the GPU (czk_kzg10_*).
 struct KZG10 {
+    // g, gamma_g, h, beta_h resident on the context's GPU
+    class VerifierKey {
+      public:
+        VerifierKey(const Context& ctx, const G1AffinePoint& g, const G1AffinePoint& gamma_g, const G2AffinePoint& h, const G2AffinePoint& beta_h)
+            : g(g), gamma_g(gamma_g), h(h), beta_h(beta_h), ctx_(&ctx) {
+            ctx.check(czk_kzg10_vk_create(ctx.raw(), g.x.l, gamma_g.x.l, h.x.c0.l, beta_h.x.c0.l, &vk_));
+        }
+        ~VerifierKey() { czk_kzg10_vk_release(vk_); }
+        VerifierKey(const VerifierKey&) = delete;
+        VerifierKey& operator=(const VerifierKey&) = delete;
+        const Context& ctx() const { return *ctx_; }
+        const czk_kzg10_vk* raw() const { return vk_; }
+        const G1AffinePoint g, gamma_g;
+        const G2AffinePoint h, beta_h;
+
+      private:
+        const Context* ctx_;
+        czk_kzg10_vk* vk_ = nullptr;
+    };
+    // one opening as the verifier sees it: Commitment, point, value, Proof { w, random_v }
+    struct Opening {
+        G1AffinePoint comm;
+        Fr point, value;
+        G1AffinePoint w;
+        std::optional<Fr> random_v;
+    };
+    struct OpeningArrays {
+        std::vector<uint64_t> comm, w, points, values, random_v;
+        std::vector<uint8_t> comm_inf, w_inf;
+        bool hiding = false;
+        explicit OpeningArrays(const std::vector<Opening>& o) {
+            for (const Opening& x : o) hiding = hiding || x.random_v.has_value();
+            for (const Opening& x : o) {
+                comm.insert(comm.end(), x.comm.x.l, x.comm.x.l + 6);
+                comm.insert(comm.end(), x.comm.y.l, x.comm.y.l + 6);
+                w.insert(w.end(), x.w.x.l, x.w.x.l + 6);
+                w.insert(w.end(), x.w.y.l, x.w.y.l + 6);
+                points.insert(points.end(), x.point.l, x.point.l + 4);
+                values.insert(values.end(), x.value.l, x.value.l + 4);
+                comm_inf.push_back(x.comm.infinity);
+                w_inf.push_back(x.w.infinity);
+                const Fr rv = x.random_v.value_or(Fr{{0, 0, 0, 0}});   // zero decides as None
+                if (hiding) random_v.insert(random_v.end(), rv.l, rv.l + 4);
+            }
+        }
+    };
+    // KZG10::check for each opening: k independent verdicts
+    static std::vector<bool> check(const VerifierKey& vk, const std::vector<Opening>& openings) {
+        const OpeningArrays a(openings);
+        std::vector<uint8_t> ok(openings.size());
+        vk.ctx().check(czk_kzg10_check(vk.ctx().raw(), vk.raw(), a.comm.data(), a.comm_inf.data(), a.points.data(), a.values.data(), a.w.data(),
+                                       a.w_inf.data(), a.hiding ? a.random_v.data() : nullptr, openings.size(), ok.data(), CZK_MEM_HOST));
+        return std::vector<bool>(ok.begin(), ok.end());
+    }
+    static bool check(const VerifierKey& vk, const Opening& opening) { return check(vk, std::vector<Opening>{opening})[0]; }
+    // KZG10::batch_check of ONE batch; randomizers: one canonical 256-bit value per opening, drawn by the caller as the reference draws them
+    // (1, then 128-bit values: mod.rs:333, :349-351)
+    static bool batch_check(const VerifierKey& vk, const std::vector<Opening>& openings, const std::vector<std::array<uint64_t, 4>>& randomizers) {
+        if (randomizers.size() != openings.size()) throw Panic(CZK_ERR_ARG, "one randomizer per opening");
+        const OpeningArrays a(openings);
+        const size_t offs[2] = {0, openings.size()};
+        uint8_t ok = 0;
+        vk.ctx().check(czk_kzg10_batch_check(vk.ctx().raw(), vk.raw(), a.comm.data(), a.comm_inf.data(), a.points.data(), a.values.data(), a.w.data(),
+                                             a.w_inf.data(), a.hiding ? a.random_v.data() : nullptr,
+                                             randomizers.empty() ? nullptr : randomizers[0].data(), offs, 1, &ok, CZK_MEM_HOST));
+        return ok != 0;
+    }
+
     static G1Projective commit(const G1Bases& powers_of_g, const std::vector<Fr>& coeffs, const G1Bases* powers_of_gamma_g = nullptr,
                                const std::vector<Fr>* blinding_coeffs = nullptr) {
         if (coeffs.size() > powers_of_g.len()) throw Panic(CZK_ERR_SIZE, "TooManyCoefficients (check_degree_is_too_large)");
@@ -648,8 +723,6 @@ struct R1CStoQAP {
 //   prepare_verifying_key, verify_proof (groth16/src/verifier.rs:12-58)                    prepare_verifying_key, verify_proof
 struct Fq6 { Fq2 c0, c1, c2; };
 struct Fq12 { Fq6 c0, c1; };   // 72 u64, the reference's nesting (czk.h)
-struct G1AffinePoint { Fq x, y; bool infinity = false; };
-struct G2AffinePoint { Fq2 x, y; bool infinity = false; };
 
 struct Bls12_377 {
     static Fq12 product_of_pairings(const Context& ctx, const std::vector<std::pair<G1AffinePoint, G2AffinePoint>>& pairs) {

@@ -31,6 +31,10 @@ pub struct czk_fixed_base {
 pub struct czk_groth16_pvk {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct czk_kzg10_vk {
+    _private: [u8; 0],
+}
 
 pub const CZK_OK: c_int = 0; // czk_status
 pub const CZK_ERR_SIZE: c_int = 1; // czk_status
@@ -178,6 +182,13 @@ extern "C" {
     pub fn czk_groth16_pvk_create(ctx: *mut czk_ctx, alpha_g1: *const u64, beta_g2: *const u64, gamma_g2: *const u64, delta_g2: *const u64, gamma_abc_g1: *const u64, gamma_abc_inf: *const u8, n_gamma_abc: usize, out: *mut *mut czk_groth16_pvk) -> c_int;
     pub fn czk_groth16_pvk_release(pvk: *mut czk_groth16_pvk);
     pub fn czk_groth16_verify(ctx: *mut czk_ctx, pvk: *const czk_groth16_pvk, a: *const u64, b: *const u64, c: *const u64, inf: *const u8, public_inputs: *const u64, m: usize, k: usize, out_ok: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_points_add(ctx: *mut czk_ctx, group: c_int, a: *const u64, a_inf: *const u8, b: *const u64, b_inf: *const u8, n: usize, negate_b: c_int, out: *mut u64, out_inf: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_points_mul(ctx: *mut czk_ctx, group: c_int, pts: *const u64, inf: *const u8, pts_stride: usize, scalars: *const u64, n: usize, scalar_form: c_int, out: *mut u64, out_inf: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_points_sum(ctx: *mut czk_ctx, group: c_int, pts: *const u64, inf: *const u8, offsets: *const usize, k: usize, out: *mut u64, out_inf: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_kzg10_vk_create(ctx: *mut czk_ctx, g: *const u64, gamma_g: *const u64, h: *const u64, beta_h: *const u64, out: *mut *mut czk_kzg10_vk) -> c_int;
+    pub fn czk_kzg10_vk_release(vk: *mut czk_kzg10_vk);
+    pub fn czk_kzg10_check(ctx: *mut czk_ctx, vk: *const czk_kzg10_vk, comm: *const u64, comm_inf: *const u8, points: *const u64, values: *const u64, w: *const u64, w_inf: *const u8, random_v: *const u64, k: usize, out_ok: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_kzg10_batch_check(ctx: *mut czk_ctx, vk: *const czk_kzg10_vk, comm: *const u64, comm_inf: *const u8, points: *const u64, values: *const u64, w: *const u64, w_inf: *const u8, random_v: *const u64, randomizers: *const u64, offsets: *const usize, b: usize, out_ok: *mut u8, mem: c_int) -> c_int;
     pub fn czk_profile_enable(ctx: *mut czk_ctx, on: c_int) -> c_int;
     pub fn czk_profile_reset(ctx: *mut czk_ctx) -> c_int;
     pub fn czk_profile_read(ctx: *mut czk_ctx, kernel: *const c_char, total_ms: *mut f64, launches: *mut u64) -> c_int;
