@@ -16,3 +16,4 @@ from . import parallel  # noqa: F401
 from . import keygen  # noqa: F401
 from . import keyio  # noqa: F401
 from . import kzg  # noqa: F401
+from . import marlin  # noqa: F401

@@ -505,6 +505,20 @@ class Context:
         self._ck(self._L.czk_r1cs_matvec(self._h, mat._h, _ptr(z), C.c_size_t(z_stride), C.c_size_t(lanes), _ptr(out), C.c_size_t(out_stride), C.c_int(mem)))
         return out
 
+    def marlin_arithmetize(self, row_ptr, col_idx, coeff, log_h: int, log_x: int, n_instance: int, k: int, out=None, mem=CZK_MEM_HOST, m=None, nnz=None):
+        """arithmetize_matrix for one CSR matrix up to the evaluations on K (czk_marlin_arithmetize); host mode takes numpy arrays and returns
+        (4, k, 4): row, col, val, row_col.  Device mode: pointers, with m / nnz given and `out` a device buffer of 4 k Fr."""
+        if mem == CZK_MEM_HOST:
+            row_ptr = np.ascontiguousarray(row_ptr, np.uint64)
+            col_idx = np.ascontiguousarray(col_idx, np.uint32)
+            coeff = np.ascontiguousarray(coeff, np.uint64)
+            m, nnz = row_ptr.size - 1, col_idx.size
+            out = np.zeros((4, k, 4), dtype=np.uint64)
+        self._ck(self._L.czk_marlin_arithmetize(self._h, _ptr(row_ptr), _ptr(col_idx if nnz else None), _ptr(coeff if nnz else None), C.c_size_t(m),
+                                              C.c_size_t(nnz), C.c_uint(log_h), C.c_uint(log_x), C.c_size_t(n_instance), C.c_size_t(k),
+                                              _ptr(out if k else None), C.c_int(mem)))
+        return out
+
     def poly_div_linear(self, coeffs, z, lanes: int = 1, n=None, quotient=None, remainder=None, mem=CZK_MEM_HOST):
         """coeffs / (X - z) per lane; host mode returns (quotient (lanes, n-1, 4), remainder (lanes, 4))."""
         z = np.ascontiguousarray(z, np.uint64).reshape(4)

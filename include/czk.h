@@ -374,6 +374,18 @@ void czk_r1cs_matrix_release(czk_r1cs_matrix* a);
  * (out_stride >= m; elements [m, out_stride) are not written, so the caller's zero padding to the domain size stays). */
 int czk_r1cs_matvec(czk_ctx* ctx, const czk_r1cs_matrix* a, const uint64_t* z, size_t z_stride, size_t lanes, uint64_t* out,
                     size_t out_stride, int mem);
+/* arithmetize_matrix (marlin/src/ahp/constraint_systems.rs:152-262) for one matrix of a squared, balanced R1CS, up to the evaluations on K: the CSR
+ * arrays as czk_r1cs_matrix_register takes them (m rows = constraints, col_idx into [instance | witness] with n_instance formatted inputs, coeff
+ * Montgomery Fr), H = 2^log_h (the constraint domain), X = 2^log_x (the input domain), k = |K| slots.  out: 4 x k Fr, row | col | val | row_col.
+ * For entry t of constraint r at variable i: i' = i for i < n_instance, else i + (X - n_instance) (pad_input_for_indexer_and_prover),
+ * p = reindex_by_subdomain(H, X, i'), and with w = get_root_of_unity(H)
+ *   row[t] = w^p, col[t] = w^r (the transpose of M, :191-194), val[t] = coeff[t] w^p / |H| (= coeff / u_H(w^p, w^p), :195-204), row_col[t] = row[t] col[t];
+ * slots nnz <= t < k hold row = col = row_col = 1, val = 0 (:207-211).  Entries keep their order: the caller sorts each row by column (:183-185).
+ * CZK_ERR_SIZE for m > H, k < nnz, log_x > log_h, n_instance > X or log_h > 31.  CZK_MEM_HOST: CZK_ERR_ARG for a malformed row_ptr or an index that
+ * has no position on H (>= H - X + n_instance); the call blocks.  CZK_MEM_DEVICE: the call only enqueues on the context's stream and cannot read the
+ * arrays, so their contents are the caller's to check; slots of malformed entries are unspecified, and nothing outside the arrays is accessed. */
+int czk_marlin_arithmetize(czk_ctx* ctx, const uint64_t* row_ptr, const uint32_t* col_idx, const uint64_t* coeff, size_t m, size_t nnz,
+                           unsigned log_h, unsigned log_x, size_t n_instance, size_t k, uint64_t* out, int mem);
 /* DensePolynomial / (X - z): KZG10::compute_witness_polynomial (poly-commit/src/kzg10/mod.rs:200-224; shares divide
  * lane-wise because the divisor is public, mpc-algebra/src/share/add.rs:148-156).  coeffs: lanes x n Fr, low degree
  * first; quotient: lanes x (n-1) Fr; remainder (may be NULL): lanes Fr = p(z), which is also

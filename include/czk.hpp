@@ -680,6 +680,16 @@ struct ConstraintMatrix {
     }
 };
 
+// arithmetize_matrix (marlin/src/ahp/constraint_systems.rs:152-262) for one matrix in CSR form, up to the evaluations on K: 4 x k elements,
+// row | col | val | row_col.  H = 2^log_h, X = 2^log_x; the matrix is squared and balanced and its rows are sorted by column already.
+inline std::vector<Fr> marlin_arithmetize(const Context& ctx, const uint64_t* row_ptr, const uint32_t* col, const Fr* coeff, size_t rows, size_t nnz,
+                                          unsigned log_h, unsigned log_x, size_t n_instance, size_t k) {
+    std::vector<Fr> out(4 * k, Fr{{0, 0, 0, 0}});
+    ctx.check(czk_marlin_arithmetize(ctx.raw(), row_ptr, col, nnz ? coeff->l : nullptr, rows, nnz, log_h, log_x, n_instance, k, k ? out[0].l : nullptr,
+                                     CZK_MEM_HOST));
+    return out;
+}
+
 // mpc-snarks/src/groth/r1cs_to_qap.rs:47-113 -- the NTT / pointwise sequence of witness_map for a single prover
 // (T = Fr).  `a`, `b`, `c` are the evaluated constraint rows (a[0..N), then the instance copy; :67-83, :95-100).
 // `batch_product` is F::batch_product_in_place (:92) -- a plain product here, the Beaver protocol for shares.
