@@ -45,7 +45,7 @@ struct GT<Fq2> {
     static constexpr int AW = 24, JW = 36, FW = 12, XW = 48;
 };
 
-// COEFF_B of y^2 = x^3 + b, Montgomery form (k_subgroup_check in msm.hip, the point decoder in point_codec.hip)
+// COEFF_B of y^2 = x^3 + b, Montgomery form (k_subgroup_check in msm_bases.hip, the point decoder in point_codec.hip)
 template <class F>
 struct CurveB;
 template <>
@@ -82,7 +82,7 @@ struct DeviceBuf {
 };
 // What a slot's sort workspace holds when it was made from CZK_MEM_STABLE scalars: a CZK_MEM_SAME_SCALARS call that matches a slot's key in every field reads that
 // slot's sorted entries instead of sorting again.  Cleared by czk_ctx_sync / czk_ctx_wait_mark; overwritten by the slot's next sort.
-struct MsmSortKey {
+struct MsmSortKey {   // (msm.hip msm_sort_source fills a key as one aggregate: a new field goes at the END)
     bool valid = false;
     uint64_t seq = 0;          // the call that made the sort (czk_ctx::msm_seq)
     const void* scalars = nullptr;
@@ -97,7 +97,7 @@ struct MsmSlot {
     bool used = false;
     MsmSortKey key;
 };
-struct MsmPending {   // a host result on its way: pinned staging -> the caller's buffer at czk_ctx_sync / czk_ctx_wait_mark (MSM results, deferred downloads)
+struct MsmPending {   // (msm.hip msm_enqueue fills this as one aggregate: a new field goes at the END)  A host result on its way: pinned staging -> the caller's buffer at czk_ctx_sync / czk_ctx_wait_mark (MSM results, deferred downloads)
     const char* src;
     void* dst;
     size_t bytes;
@@ -147,7 +147,7 @@ struct czk_ctx {
     // lab build alone (libczk_hip_lab.so, -DCZK_LAB: the measured-and-rejected variants of EXPERIMENTS.md) and is fixed at its default otherwise.
     bool msm_sort_reuse = false;     // "msm_sort_reuse": CZK_MEM_SAME_SCALARS calls read an earlier call's digit sort when the layouts match (default off: measured, EXPERIMENTS.md section 14)
     bool msm_sort_reuse_any_inf = false;   // lab "msm_sort_reuse_any_inf": ... even when the keys' points at infinity differ (WRONG results: the upper bound of sharing one sort per scalar vector)
-    bool msm_sort_onepass = false;   // "msm_sort_onepass": the single-pass digit sort for every call (it is the > 2048-partition fallback anyway)
+    bool msm_sort_onepass = false;   // "msm_sort_onepass": the single-pass digit sort for every call (the only way to reach it: a call never has more than 2048 partitions)
     bool msm_fixed_c = false;        // "msm_fixed_c": keys registered from now on keep their own window width for short calls (no secondary table sets)
     unsigned msm_c_g1 = 0, msm_c_g2 = 0;   // "msm_window_g1" / "msm_window_g2": primary window width of keys registered from now on (0 = cost model)
     bool msm_launch_split = false;   // (set by msm_enqueue for the launch it is making: a table-free call, lanes = windows)
@@ -193,7 +193,7 @@ struct czk_ctx {
 
 // A second (third, ...) set of window tables over a PREFIX of a registered base array, at a narrower window width: short MSMs
 // under a long key (KZG commitments of low-degree polynomials under `powers_of_g`, poly-commit/src/kzg10/mod.rs:159-162) would
-// otherwise pay the key's 2^(c-1)-bucket reduction per call.  Built on first use by msm.hip (pick_tables), immutable afterwards.
+// otherwise pay the key's 2^(c-1)-bucket reduction per call.  Built on first use by msm_bases.hip (pick_tables), immutable afterwards.
 struct czk_table_set {
     unsigned c = 0, W = 0;
     size_t cover = 0;          // points covered = stride between windows
@@ -367,8 +367,40 @@ int msm_pinned_take(czk_ctx* ctx, size_t bytes, char** out);   // staging for on
 int ctx_mark(czk_ctx* ctx, uint64_t* out);       // czk_ctx_mark / czk_ctx_wait_mark
 int ctx_wait_mark(czk_ctx* ctx, uint64_t id);
 void msm_pipeline_destroy(czk_ctx* ctx);
+// implemented in msm_bases.hip
 int fixed_base_points_device(czk_ctx* ctx, int group, const u64* k_dev, size_t n, u64* out_dev);
 void launch_batch_to_affine(hipStream_t st, int group, const u64* jac, size_t n, u64* scratch, u64* out_aff, uint8_t* out_inf);   // Montgomery's trick, 32 points per inversion
+// the table set an MSM of `size` pairs runs on (build: make the secondary set the cost model asks for when none fits); the window width such a call asks for
+int pick_tables(czk_ctx* ctx, const czk_bases* b, size_t size, czk_table_set* tv, bool build);
+unsigned msm_width_for(const czk_bases* b, size_t size);
+// implemented in msm_sort.hip: the digit sort of one MSM call.  The constants size its workspace (msm.hip) and bound choose_c_split (msm_bases.hip).
+// partitioned sort: partitions of PART_BUCKETS buckets; k_digits_part keeps its partition histograms (one per window for table-free keys,
+// which is what bounds choose_c_split) in an LDS array of MAX_PARTS counters
+constexpr unsigned PART_LOG = 10, PART_BUCKETS = 1u << PART_LOG, MAX_PARTS = 2048;
+constexpr unsigned CNT_BINS = 2048;         // population order: bucket populations of CNT_BINS - 1 and more share the last bin
+constexpr unsigned SCAN_TILE = 2048;        // one-pass sort: entries per tile of the offset scan
+constexpr unsigned PSORT_THREADS = 1024;    // k_part_sort: threads per partition
+#ifndef CZK_PS_TILE
+#define CZK_PS_TILE 16
+#endif
+constexpr unsigned PS_TILE = CZK_PS_TILE;   // k_part_scatter: entries per thread
+inline size_t part_scatter_lds(unsigned nt, unsigned n_parts) { return (size_t)(3 * n_parts + nt) * 4 + (size_t)nt * PS_TILE * (4 + 2 + 2); }
+
+// What one call's sort is made from (msm.hip: the head of the call's plan), and the arrays it fills, carved from a slot's sort workspace (msm.hip msm_carve)
+struct MsmSortDims {
+    const u64* scalars;   // real_lanes x n_scalars, of which the first `size` of each vector are used
+    czk_table_set tv;     // the table set in use, not owned (its infinity flags drop digits)
+    size_t n_scalars, size, nb, lanes, real_lanes, B, total, n_tiles, lds_per_block;   // nb: points per window; lanes: bucket sets; total = W * size entries per lane
+    unsigned c, Wd, W, n_parts, part_shift;   // Wd digit windows per scalar, W windows per bucket set (table-free keys: 1, and lanes = real_lanes * Wd)
+    int form;
+    bool split, one_pass;
+};
+struct MsmSortBufs {   // per lane: digits, sorted, ranks (the partitioned sort's entries grouped by partition), part_lb: total; part_*: n_parts (+ 1); counts, offsets, perm: B
+    u32 *digits, *sorted, *ranks, *part_counts, *part_cursor, *part_base, *counts, *offsets, *perm, *chist, *tile_sums;
+    uint16_t* part_lb;
+};
+// Enqueues on `st`: digits -> sorted entries with per-bucket counts / offsets -> buckets in descending-population order (perm).
+hipError_t msm_sort_enqueue(hipStream_t st, const MsmSortDims& d, const MsmSortBufs& s);
 // implemented in point_ops.hip: czk_points_add / _mul / _sum over DEVICE buffers (flags may be null = none infinite; a stride of 0 repeats one point;
 // offs_host: k + 1 host offsets, already validated).  Each only enqueues on the context's stream.
 int points_add_device(czk_ctx* ctx, int group, const u64* a, const uint8_t* a_inf, size_t a_stride, const u64* b, const uint8_t* b_inf, size_t b_stride,

@@ -11,7 +11,7 @@
 //     full, so that its carry can leave it (k = r - 1 at w = 11 does).
 //   * built on the device: window bases 2^(w j) P by doubling (one thread each), normalised; then one thread per chunk of 32 consecutive
 //     multiples -- the chunk's first entry by double-and-add, the rest by a running mixed addition of the window base -- and ONE batched
-//     normalisation of the whole table (msm.hip's k_batch_to_affine through launch_batch_to_affine).
+//     normalisation of the whole table (msm_bases.hip's k_batch_to_affine through launch_batch_to_affine).
 //   * multiply: one thread per scalar, Jacobian accumulator, curve.h's complete jac_add_mixed (P = +-Q and infinity included) -- not the
 //     twisted Edwards path, which is exact in the subgroup only.  Scalars are decoded from Montgomery form on the fly; bits at and above
 //     253 are ignored (fixed_base.rs:72).

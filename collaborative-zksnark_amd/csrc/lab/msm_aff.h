@@ -68,7 +68,7 @@ __device__ __forceinline__ void lvl_store(uint4* lvl, size_t slot, const AffPoin
     lvl_store_coord(lvl, slot, 0, p.x, p.flags);
     lvl_store_coord(lvl, slot, 4, p.y, 0u);
 }
-// table entry (x R', y R' as canonical 12 x u32; msm.hip register_impl) -> unsaturated point; a negative digit adds -P
+// table entry (x R', y R' as canonical 12 x u32; msm_bases.hip register_impl) -> unsaturated point; a negative digit adds -P
 __device__ __forceinline__ void table_load_x(const u64* pts, u32 code, FqU& x) { x = fqu_unpack(fp_load<FqParams>(pts + (size_t)12 * (code & 0x7fffffffu))); }
 __device__ __forceinline__ void table_load_y(const u64* pts, u32 code, FqU& y) {
     y = fqu_unpack(fp_load<FqParams>(pts + (size_t)12 * (code & 0x7fffffffu) + 6));

@@ -7,7 +7,7 @@
 //   czk_points_sum ... out[j] = sum of a segment   add_assign (:666-728) in a tree: one wave per segment, partial sums combined through LDS
 // Points are affine Montgomery + one infinity byte, as everywhere in the ABI; no call makes a subgroup assumption (curve.h's jac_add_mixed /
 // jac_add / jac_double are complete: P = Q doubles, P = -Q and 2 * (x, 0) leave z = 0).  Each kernel writes Jacobian triples into a workspace and
-// ONE batched normalisation per launch (msm.hip's k_batch_to_affine through launch_batch_to_affine, as fixed_base.hip) writes the affine results:
+// ONE batched normalisation per launch (msm_bases.hip's k_batch_to_affine through launch_batch_to_affine, as fixed_base.hip) writes the affine results:
 // infinity is flag 1 with the coordinates (0, 1).
 // All arithmetic is the 32-bit-limb integer VALU code of field.h / curve.h, with the Montgomery multiply out of line (-DCZK_NOINLINE_MUL).
 #include "czk_internal.h"

@@ -129,7 +129,7 @@ const char* czk_version(void);
  *   "msm_sort_reuse" 0/1        honour CZK_MEM_SAME_SCALARS between keys registered AFTERWARDS (default 0 = every call sorts: sharing b_g2's sort with b_g1 measured + 0.5 % per proof when the two
  *                               calls are neighbours, - 0.6 % two calls apart -- the sorts run beside the accumulate kernels anyway, and entries sorted a moment
  *                               ago are still in the last-level cache when their own accumulate kernel reads them)
- *   "msm_sort_onepass" 0/1      single-pass digit sort for every call (default: only beyond 2048 partitions)
+ *   "msm_sort_onepass" 0/1      single-pass digit sort for every call (default: never -- the partitioned sort)
  *   "msm_fixed_c" 0/1           keys registered AFTERWARDS keep their own window width for short calls (no secondary table sets)
  *   "msm_window_g1" / "msm_window_g2" 0, 8..22   primary window width of keys registered AFTERWARDS (0 = the cost model, default)
  *   "ntt_gen1" 0/1              first-generation NTT passes (the small-domain kernels) for every size

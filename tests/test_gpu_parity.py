@@ -435,8 +435,8 @@ def test_msm_fallback_reductions_still_match(czk, orc, g, envs):
 
 
 def test_msm_one_pass_sort_still_matches(czk, orc):
-    """The option "msm_sort_onepass" selects the single-pass counting sort (one global atomic + one random store per entry), the
-    fallback for more than 2048 partitions; keep it covered (product library)."""
+    """The option "msm_sort_onepass" selects the single-pass counting sort (one global atomic + one random store per entry), which
+    nothing else reaches (a call never has more than 2048 partitions); keep it covered (product library)."""
     c2 = czk.Context(0, options={"msm_sort_onepass": 1})
     n = 5000
     _, bases = _bases(c2, 1, n, 43)
@@ -447,6 +447,27 @@ def test_msm_one_pass_sort_still_matches(czk, orc):
     got = c2.msm(b, sc, lanes=2)
     for ln in range(2):
         assert _same_point(c2, orc, 1, got[ln], orc.msm(1, bases, inf, sc[ln]))
+    b.release()
+    c2.close()
+
+
+@pytest.mark.parametrize("c,lanes", [(13, 2), (20, 2), (21, 2), (22, 1)])
+def test_msm_partition_scatter_widths(czk, orc, c, lanes):
+    """Sorts with 4 / 512 / 1024 / 2048 partitions of 1024 buckets (c = 13 / 20 / 21 / 22) give the right result: the partition counts at which
+    the scatter is launched with 256, 512, 512 and 1024 threads, which otherwise only calls of 2^20 points and more reach.  (Any thread count
+    sorts correctly, so this covers each launch, not the choice between them.)  The key keeps its own width for this short call ("msm_fixed_c"), and one workspace slot (one lane at
+    c = 22) keeps the bucket workspace near 0.6 GB."""
+    c2 = czk.Context(0, options={"msm_slots": 1, "msm_window_g1": c, "msm_fixed_c": 1})
+    n = 300
+    _, bases = _bases(c2, 1, n, 45)
+    sc = rand_fr_canonical(46, lanes * n).reshape(lanes, n, 4)
+    inf = np.zeros(n, dtype=np.uint8)
+    inf[[3, 250]] = 1
+    b = c2.register_bases(1, bases, inf)
+    assert b.layout_for(n)[0] == c
+    got = c2.msm(b, sc, lanes=lanes)
+    for ln in range(lanes):
+        assert _same_point(c2, orc, 1, got[ln], orc.msm(1, bases, inf, sc[ln])), (c, ln)
     b.release()
     c2.close()
 

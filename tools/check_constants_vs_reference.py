@@ -7,7 +7,7 @@ Build-container tool (needs /root/reference; it is absent on the GPU box).  It p
 writes what it found to tests/golden/reference_constants.json (DATA only: names and numbers, plus the SHA-256 of each parsed
 file), and then asserts that the constants carried by
     oracle/pyref.py, oracle/czk_oracle.c            (the checker)
-    collaborative-zksnark_amd/csrc/field.h, fqu.h, msm.hip, ntt.hip   (the product)
+    collaborative-zksnark_amd/csrc/field.h, fqu.h, msm_bases.hip, ntt.hip   (the product)
 equal them.  tests/test_reference_constants.py repeats the second half against the committed fixture on any machine and, where
 /root/reference exists, the first half too.
 
@@ -116,14 +116,14 @@ def repo_constants() -> dict:
             m = re.search(r"u32 " + fn + r"\(int i\)\s*\{\s*constexpr u32 m\[\d+\]\s*=\s*\{(.*?)\};", body, flags=re.S)
             prod[f"{key}.{name}"] = limbs_int([int(t.strip().rstrip("u"), 16) for t in m.group(1).split(",") if t.strip()], 32)
     got["field.h"] = prod
-    # product: fqu.h 28-bit limbs of the Fq modulus; msm.hip generators (Montgomery, 32-bit limbs); ntt.hip LARGE root
+    # product: fqu.h 28-bit limbs of the Fq modulus; msm_bases.hip generators (Montgomery, 32-bit limbs); ntt.hip LARGE root
     utxt = open(os.path.join(ROOT, "collaborative-zksnark_amd", "csrc", "fqu.h")).read()
     m = re.search(r"u32 fqu_p\(int i\)\s*\{\s*constexpr u32 m\[14\]\s*=\s*\{(.*?)\};", utxt, flags=re.S)
     got["fqu.h"] = {"fq.MODULUS": limbs_int([int(t.strip().rstrip("u"), 16) for t in m.group(1).split(",") if t.strip()], 28)}
-    mtxt = open(os.path.join(ROOT, "collaborative-zksnark_amd", "csrc", "msm.hip")).read()
+    mtxt = open(os.path.join(ROOT, "collaborative-zksnark_amd", "csrc", "msm_bases.hip")).read()
     arr = {m.group(1): limbs_int([int(t.strip().rstrip("u"), 16) for t in m.group(2).split(",") if t.strip()], 32)
            for m in re.finditer(r"const u32 (\w+)\[12\]\s*=\s*\{(.*?)\};", mtxt, flags=re.S)}
-    got["msm.hip (Montgomery form)"] = {"g1.G1_GENERATOR_X": arr["gx"], "g1.G1_GENERATOR_Y": arr["gy"], "g2.G2_GENERATOR_X_C0": arr["x0"],
+    got["msm_bases.hip (Montgomery form)"] = {"g1.G1_GENERATOR_X": arr["gx"], "g1.G1_GENERATOR_Y": arr["gy"], "g2.G2_GENERATOR_X_C0": arr["x0"],
                                         "g2.G2_GENERATOR_X_C1": arr["x1"], "g2.G2_GENERATOR_Y_C0": arr["y0"], "g2.G2_GENERATOR_Y_C1": arr["y1"]}
     ntxt = open(os.path.join(ROOT, "collaborative-zksnark_amd", "csrc", "ntt.hip")).read()
     m = re.search(r"const u32 lr\[8\]\s*=\s*\{(.*?)\};", ntxt, flags=re.S)
