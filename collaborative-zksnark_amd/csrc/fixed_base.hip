@@ -16,7 +16,7 @@
 //     twisted Edwards path, which is exact in the subgroup only.  Scalars are decoded from Montgomery form on the fly; bits at and above
 //     253 are ignored (fixed_base.rs:72).
 // All arithmetic is the 32-bit-limb integer VALU code of field.h / curve.h.
-#include "czk_internal.h"
+#include "call.h"
 
 struct czk_fixed_base {
     int device = 0;
@@ -136,9 +136,9 @@ static int fb_build(czk_ctx* ctx, czk_fixed_base* fb, const u64* base_host) {
     hipError_t e = hipMemcpyAsync(p + o_base, base_host, AW * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         ProfScope ps(ctx, "fixed_base_table");
-        hipLaunchKernelGGL(k_fb_window_bases<F>, dim3((W + 127) / 128), dim3(128), 0, ctx->stream, (const u64*)(p + o_base), fb->w, W, (u64*)(p + o_wjac));
+        hipLaunchKernelGGL(k_fb_window_bases<F>, grid_for(W), dim3(128), 0, ctx->stream, (const u64*)(p + o_base), fb->w, W, (u64*)(p + o_wjac));
         launch_batch_to_affine(ctx->stream, fb->group, (const u64*)(p + o_wjac), W, (u64*)(p + o_scr), (u64*)(p + o_waff), (uint8_t*)(p + o_winf));
-        hipLaunchKernelGGL(k_fb_table<F>, dim3((unsigned)(((size_t)W * chunks + 127) / 128)), dim3(128), 0, ctx->stream, (const u64*)(p + o_waff),
+        hipLaunchKernelGGL(k_fb_table<F>, grid_for((size_t)W * chunks), dim3(128), 0, ctx->stream, (const u64*)(p + o_waff),
                            (const uint8_t*)(p + o_winf), W, H, chunks, (u64*)(p + o_jac));
         launch_batch_to_affine(ctx->stream, fb->group, (const u64*)(p + o_jac), E, (u64*)(p + o_scr), fb->pts, fb->inf);
         e = hipGetLastError();
@@ -149,24 +149,6 @@ static int fb_build(czk_ctx* ctx, czk_fixed_base* fb, const u64* base_host) {
     return CZK_OK;
 }
 
-template <class F>
-static int fb_msm(czk_ctx* ctx, const czk_fixed_base* fb, const u64* k_dev, size_t n, int form, u64* out_dev, uint8_t* inf_dev) {
-    constexpr int JW = GT<F>::JW, FW = GT<F>::FW;
-    DeviceBuf ws;
-    CZK_TRY(stage_take(ctx, n * (JW + FW) * 8, &ws));
-    u64 *jac = (u64*)ws.p, *scr = jac + n * JW;
-    {
-        ProfScope ps(ctx, "fixed_base_msm");
-        hipLaunchKernelGGL(k_fb_mul<F>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, ctx->stream, (const u64*)fb->pts, (const uint8_t*)fb->inf, k_dev, n,
-                           form == CZK_SCALAR_MONTGOMERY ? 1 : 0, fb->w, fb->windows, jac);
-        launch_batch_to_affine(ctx->stream, fb->group, jac, n, scr, out_dev, inf_dev);
-    }
-    hipError_t e = hipGetLastError();
-    stage_give(ctx, ws);   // (re-use is ordered: every later user enqueues on the same stream)
-    if (e != hipSuccess) return set_err(ctx, CZK_ERR_HIP, std::string("fixed-base msm: ") + hipGetErrorString(e));
-    return CZK_OK;
-}
-
 }  // namespace czk
 
 using namespace czk;
@@ -174,7 +156,7 @@ using namespace czk;
 extern "C" int czk_fixed_base_create(czk_ctx* ctx, int group, const uint64_t* base_aff, unsigned window, size_t n_hint, czk_fixed_base** out) {
     if (!ctx || !out) return ctx ? set_err(ctx, CZK_ERR_ARG, "null fixed_base_create argument") : CZK_ERR_ARG;
     *out = nullptr;
-    if (group != CZK_G1 && group != CZK_G2) return set_err(ctx, CZK_ERR_ARG, "group must be CZK_G1 or CZK_G2");
+    CZK_TRY(check_group(ctx, group));
     if (!base_aff) return set_err(ctx, CZK_ERR_ARG, "null base");
     if (window > 20) return set_err(ctx, CZK_ERR_ARG, "window must be 0 (chosen by the library) or 1..20");
     // the base is ONE finite point: x = 0 with y = 0 or y = 1 is how this ABI's affine arrays write the point at infinity
@@ -228,23 +210,18 @@ extern "C" int czk_fixed_base_msm(czk_ctx* ctx, const czk_fixed_base* fb, const 
                                   uint8_t* out_inf, int mem) {
     if (!ctx || !fb) return ctx ? set_err(ctx, CZK_ERR_ARG, "null fixed_base_msm argument") : CZK_ERR_ARG;
     if (n && (!scalars || !out_aff)) return set_err(ctx, CZK_ERR_ARG, "null fixed_base_msm buffer");
-    if (scalar_form != CZK_SCALAR_CANONICAL && scalar_form != CZK_SCALAR_MONTGOMERY) return set_err(ctx, CZK_ERR_ARG, "bad scalar_form");
-    if (!valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
-    if (fb->device != ctx->device) return set_err(ctx, CZK_ERR_ARG, "the fixed-base table lives on another device");
+    CZK_TRY(check_scalar_form(ctx, scalar_form));
+    CZK_TRY(check_mem(ctx, mem));
+    CZK_TRY(check_device(ctx, fb->device, "the fixed-base table lives on another device"));
     if (!n) return CZK_OK;
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t aw = fb->group == CZK_G1 ? 12 : 24;
-    Staged sk{ctx}, so{ctx}, si{ctx};
+    Staged sk{ctx};
+    AffineOut so(ctx);
     CZK_TRY(sk.to_device(scalars, n * 32, mem));
-    CZK_TRY(so.to_device(mem == CZK_MEM_HOST ? nullptr : out_aff, n * aw * 8, mem));
-    // the normalisation always writes flags: a caller that takes none gets them into scratch
-    const bool inf_in_place = mem == CZK_MEM_DEVICE && out_inf;
-    CZK_TRY(si.to_device(inf_in_place ? out_inf : nullptr, n, inf_in_place ? CZK_MEM_DEVICE : CZK_MEM_HOST));
-    CZK_TRY(fb->group == CZK_G1 ? fb_msm<Fq>(ctx, fb, (const u64*)sk.dev, n, scalar_form, (u64*)so.dev, (uint8_t*)si.dev)
-                                : fb_msm<Fq2>(ctx, fb, (const u64*)sk.dev, n, scalar_form, (u64*)so.dev, (uint8_t*)si.dev));
-    if (mem == CZK_MEM_HOST) {
-        if (out_inf) CZK_HIP(ctx, hipMemcpyAsync(out_inf, si.dev, n, hipMemcpyDeviceToHost, ctx->stream));
-        return so.to_host(out_aff, n * aw * 8);
-    }
-    return CZK_OK;
+    CZK_TRY(so.open(fb->group, out_aff, out_inf, n, mem));
+    CZK_TRY(launch_to_affine(ctx, "fixed_base_msm", "fixed-base msm", fb->group, n, so.pts.words(), so.inf.flags(), [&](auto tag, u64* jac) {
+        hipLaunchKernelGGL(k_fb_mul<typename decltype(tag)::type>, grid_for(n), dim3(128), 0, ctx->stream, (const u64*)fb->pts, (const uint8_t*)fb->inf,
+                           (const u64*)sk.dev, n, scalar_form == CZK_SCALAR_MONTGOMERY ? 1 : 0, fb->w, fb->windows, jac);
+    }));
+    return so.close();
 }

@@ -10,7 +10,7 @@
 //   batch_check:  total_c = sum r_i (C_i + [z_i] W_i) - [sum r_i v_i] g - [sum r_i rv_i] gamma_g,  total_w = sum r_i W_i,
 //                 ok[j]  iff  e(total_w, -beta_h) * e(total_c, h) == 1   (mod.rs:358-367 negates total_w instead of beta_h)
 // As in the reference no point gets a subgroup or on-curve check, and a pair with infinity on either side is skipped by the Miller loop.
-#include "czk_internal.h"
+#include "call.h"
 #include "tower.h"
 
 struct czk_kzg10_vk {
@@ -58,32 +58,6 @@ __global__ __launch_bounds__(128) void k_kzg_pairs(const u64* p, const uint8_t* 
     g2_inf[2 * t + 1] = s_inf ? s_inf[is] : 0;
 }
 
-// device allocations of one call, freed on every return path
-struct KzgBufs {
-    czk_ctx* ctx;
-    std::vector<void*> ps;
-    explicit KzgBufs(czk_ctx* c) : ctx(c) {}
-    ~KzgBufs() {
-        for (void* p : ps) (void)hipFree(p);
-    }
-    template <class T>
-    int get(T** out, size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return set_err(ctx, CZK_ERR_NOMEM, "hipMalloc KZG10 workspace");
-        ps.push_back(p);
-        *out = (T*)p;
-        return CZK_OK;
-    }
-    int g1(u64** pts, uint8_t** inf, size_t n) {
-        CZK_TRY(get(pts, n * 96));
-        return get(inf, n);
-    }
-    int g2(u64** pts, uint8_t** inf, size_t n) {
-        CZK_TRY(get(pts, n * 192));
-        return get(inf, n);
-    }
-};
-
 // the per-opening arrays of both calls, staged into HBM for host callers
 struct KzgIn {
     Staged comm, comm_inf, points, values, w, w_inf, random_v;
@@ -102,28 +76,27 @@ struct KzgIn {
 };
 
 // verdicts of k products of two pairs each: (p, r) and (q, s)
-static int two_pair_verdicts(czk_ctx* ctx, KzgBufs& bufs, const u64* p, const uint8_t* p_inf, const u64* q, const uint8_t* q_inf, const u64* r,
+static int two_pair_verdicts(czk_ctx* ctx, CallMem& bufs, const u64* p, const uint8_t* p_inf, const u64* q, const uint8_t* q_inf, const u64* r,
                              size_t r_stride, const uint8_t* r_inf, const u64* s, size_t s_stride, const uint8_t* s_inf, size_t k, uint8_t* out_ok, int mem) {
     u64 *g1, *g2;
-    uint8_t *g1i, *g2i, *ok = mem == CZK_MEM_DEVICE ? out_ok : nullptr;
-    CZK_TRY(bufs.g1(&g1, &g1i, 2 * k));
-    CZK_TRY(bufs.g2(&g2, &g2i, 2 * k));
-    if (!ok) CZK_TRY(bufs.get(&ok, k));
-    hipLaunchKernelGGL(k_kzg_pairs, dim3((unsigned)((k + 127) / 128)), dim3(128), 0, ctx->stream, p, p_inf, q, q_inf, r, r_stride, r_inf, s, s_stride, s_inf, k,
+    uint8_t *g1i, *g2i;
+    CallOut ok(ctx);
+    CZK_TRY(bufs.points(CZK_G1, &g1, &g1i, 2 * k));
+    CZK_TRY(bufs.points(CZK_G2, &g2, &g2i, 2 * k));
+    CZK_TRY(ok.open(out_ok, k, mem, &bufs));
+    hipLaunchKernelGGL(k_kzg_pairs, grid_for(k), dim3(128), 0, ctx->stream, p, p_inf, q, q_inf, r, r_stride, r_inf, s, s_stride, s_inf, k,
                        g1, g1i, g2, g2i);
     CZK_HIP(ctx, hipGetLastError());
     std::vector<size_t> offs(k + 1);
     for (size_t t = 0; t <= k; t++) offs[t] = 2 * t;
-    CZK_TRY(pairing_is_one_device(ctx, g1, g1i, g2, g2i, offs.data(), k, ok));   // (blocks: every buffer of the call is idle afterwards)
-    if (mem == CZK_MEM_HOST) CZK_HIP(ctx, hipMemcpy(out_ok, ok, k, hipMemcpyDeviceToHost));
-    return CZK_OK;
+    CZK_TRY(pairing_is_one_device(ctx, g1, g1i, g2, g2i, offs.data(), k, ok.flags()));   // (blocks: every buffer of the call is idle afterwards)
+    return ok.close();
 }
 
 static int kzg_args(czk_ctx* ctx, const czk_kzg10_vk* vk, int mem) {
     if (!vk) return set_err(ctx, CZK_ERR_ARG, "null verifier key");
-    if (!valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
-    if (vk->device != ctx->device) return set_err(ctx, CZK_ERR_ARG, "verifier key lives on another device");
-    return CZK_OK;
+    CZK_TRY(check_mem(ctx, mem));
+    return check_device(ctx, vk->device, "verifier key lives on another device");
 }
 
 }  // namespace czk
@@ -166,15 +139,15 @@ extern "C" int czk_kzg10_check(czk_ctx* ctx, const czk_kzg10_vk* vk, const uint6
     if (!k) return CZK_OK;
     if (!comm || !points || !values || !w || !out_ok) return set_err(ctx, CZK_ERR_ARG, "null opening argument");
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    KzgBufs bufs(ctx);
+    CallMem bufs(ctx, "KZG10 workspace");
     KzgIn in(ctx);
     CZK_TRY(in.open(comm, comm_inf, points, values, w, w_inf, random_v, k, mem));
     u64 *t, *inner, *zh, *q;
     uint8_t *ti, *inner_i, *zhi, *qi;
-    CZK_TRY(bufs.g1(&t, &ti, k));
-    CZK_TRY(bufs.g1(&inner, &inner_i, k));
-    CZK_TRY(bufs.g2(&zh, &zhi, k));
-    CZK_TRY(bufs.g2(&q, &qi, k));
+    CZK_TRY(bufs.points(CZK_G1, &t, &ti, k));
+    CZK_TRY(bufs.points(CZK_G1, &inner, &inner_i, k));
+    CZK_TRY(bufs.points(CZK_G2, &zh, &zhi, k));
+    CZK_TRY(bufs.points(CZK_G2, &q, &qi, k));
     const int mont = CZK_SCALAR_MONTGOMERY;
     // inner = C - [v] g - [rv] gamma_g  (mod.rs:303-306)
     CZK_TRY(points_mul_device(ctx, CZK_G1, vk->g(), nullptr, 0, (const u64*)in.values.dev, k, mont, t, ti));
@@ -196,13 +169,11 @@ extern "C" int czk_kzg10_batch_check(czk_ctx* ctx, const czk_kzg10_vk* vk, const
     CZK_TRY(kzg_args(ctx, vk, mem));
     if (!b) return CZK_OK;
     if (!offsets || !out_ok) return set_err(ctx, CZK_ERR_ARG, "null batch argument");
-    if (offsets[0] != 0) return set_err(ctx, CZK_ERR_ARG, "offsets[0] must be 0");
-    for (size_t j = 0; j < b; j++)
-        if (offsets[j + 1] < offsets[j]) return set_err(ctx, CZK_ERR_ARG, "offsets must be non-decreasing");
-    const size_t k = offsets[b];
+    size_t k;
+    CZK_TRY(check_offsets(ctx, offsets, b, &k));
     if (k && (!comm || !points || !values || !w || !randomizers)) return set_err(ctx, CZK_ERR_ARG, "null opening argument");
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    KzgBufs bufs(ctx);
+    CallMem bufs(ctx, "KZG10 workspace");
     KzgIn in(ctx);
     Staged sr{ctx};
     CZK_TRY(in.open(comm, comm_inf, points, values, w, w_inf, random_v, k, mem));
@@ -210,12 +181,12 @@ extern "C" int czk_kzg10_batch_check(czk_ctx* ctx, const czk_kzg10_vk* vk, const
     u64 *t, *rc, *rw, *tc, *tw, *gs, *rm, *prod, *mult;
     uint8_t *ti, *rci, *rwi, *tci, *twi, *gsi;
     size_t* offs;
-    CZK_TRY(bufs.g1(&t, &ti, k));
-    CZK_TRY(bufs.g1(&rc, &rci, k));
-    CZK_TRY(bufs.g1(&rw, &rwi, k));
-    CZK_TRY(bufs.g1(&tc, &tci, b));
-    CZK_TRY(bufs.g1(&tw, &twi, b));
-    CZK_TRY(bufs.g1(&gs, &gsi, b));
+    CZK_TRY(bufs.points(CZK_G1, &t, &ti, k));
+    CZK_TRY(bufs.points(CZK_G1, &rc, &rci, k));
+    CZK_TRY(bufs.points(CZK_G1, &rw, &rwi, k));
+    CZK_TRY(bufs.points(CZK_G1, &tc, &tci, b));
+    CZK_TRY(bufs.points(CZK_G1, &tw, &twi, b));
+    CZK_TRY(bufs.points(CZK_G1, &gs, &gsi, b));
     CZK_TRY(bufs.get(&rm, k * 32));
     CZK_TRY(bufs.get(&prod, k * 32));
     CZK_TRY(bufs.get(&mult, b * 32));
@@ -235,7 +206,7 @@ extern "C" int czk_kzg10_batch_check(czk_ctx* ctx, const czk_kzg10_vk* vk, const
     for (int pass = 0; pass < (random_v ? 2 : 1); pass++) {
         const u64* x = (const u64*)(pass ? in.random_v.dev : in.values.dev);
         if (k) CZK_TRY(czk_fr_vec_op(ctx, CZK_OP_MUL, rm, x, prod, k, CZK_MEM_DEVICE));
-        hipLaunchKernelGGL(k_fr_segment_sum, dim3((unsigned)((b + 127) / 128)), dim3(128), 0, ctx->stream, (const u64*)prod, (const size_t*)offs, b, mult);
+        hipLaunchKernelGGL(k_fr_segment_sum, grid_for(b), dim3(128), 0, ctx->stream, (const u64*)prod, (const size_t*)offs, b, mult);
         CZK_HIP(ctx, hipGetLastError());
         CZK_TRY(points_mul_device(ctx, CZK_G1, pass ? vk->gamma_g() : vk->g(), nullptr, 0, mult, b, CZK_SCALAR_MONTGOMERY, gs, gsi));
         CZK_TRY(points_add_device(ctx, CZK_G1, tc, tci, 1, gs, gsi, 1, b, 1, tc, tci));

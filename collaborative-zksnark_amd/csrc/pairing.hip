@@ -15,7 +15,7 @@
 // Lines of the per-proof G2 points (B) come from k_g2_prepare into a k x 19.9 KB buffer, also SoA: one code path for every
 // G2 operand (shared key lines read with stride 1, per-thread lines with stride k), and the doubling / addition steps run once
 // per point instead of once per product that uses it (czk_pairing_product may repeat a point).
-#include "czk_internal.h"
+#include "call.h"
 #include "tower.h"
 
 namespace czk {
@@ -222,41 +222,8 @@ __global__ __launch_bounds__(PAIR_BLOCK) void k_groth16_check(const u64* a, cons
 }
 
 // ------------------------------------------------------------------------------------------------- host side
-// device allocations of one call, freed on every return path
-struct CallBufs {
-    czk_ctx* ctx;
-    std::vector<void*> ps;
-    explicit CallBufs(czk_ctx* c) : ctx(c) {}
-    ~CallBufs() {
-        for (void* p : ps) (void)hipFree(p);
-    }
-    template <class T>
-    int get(T** out, size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return set_err(ctx, CZK_ERR_NOMEM, "hipMalloc pairing workspace");
-        ps.push_back(p);
-        *out = (T*)p;
-        return CZK_OK;
-    }
-    // `src` used in place (device memory) or copied in (host memory); null stays null
-    template <class T>
-    int in(const T* src, size_t bytes, int mem, const T** out) {
-        if (!src || mem == CZK_MEM_DEVICE) {
-            *out = src;
-            return CZK_OK;
-        }
-        T* d;
-        CZK_TRY(get(&d, bytes));
-        CZK_HIP(ctx, hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        *out = d;
-        return CZK_OK;
-    }
-};
-
-static unsigned blocks(size_t n) { return (unsigned)((n + PAIR_BLOCK - 1) / PAIR_BLOCK); }
-
 // products of pairings over device inputs; offs_host: k + 1 offsets; out / is_one device (either may be null)
-static int pairing_products_device(czk_ctx* ctx, CallBufs& cb, const u64* g1, const uint8_t* g1_inf, const u64* g2, const uint8_t* g2_inf,
+static int pairing_products_device(czk_ctx* ctx, CallMem& cb, const u64* g1, const uint8_t* g1_inf, const u64* g2, const uint8_t* g2_inf,
                                    const size_t* offs_host, size_t k, u64* out, uint8_t* is_one) {
     const size_t n = offs_host[k];
     u64 *lines = nullptr, *ws = nullptr;
@@ -267,11 +234,11 @@ static int pairing_products_device(czk_ctx* ctx, CallBufs& cb, const u64* g1, co
     CZK_HIP(ctx, hipMemcpyAsync(offs, offs_host, (k + 1) * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
     if (n) {
         ProfScope ps(ctx, "pairing_g2_prepare", ctx->stream);
-        hipLaunchKernelGGL(k_g2_prepare, dim3(blocks(n)), dim3(PAIR_BLOCK), 0, ctx->stream, g2, g2_inf, n, lines);
+        hipLaunchKernelGGL(k_g2_prepare, grid_for(n, PAIR_BLOCK), dim3(PAIR_BLOCK), 0, ctx->stream, g2, g2_inf, n, lines);
     }
     {
         ProfScope ps(ctx, "pairing_miller_fexp", ctx->stream);
-        hipLaunchKernelGGL(k_pairing_product, dim3(blocks(k)), dim3(PAIR_BLOCK), 0, ctx->stream, g1, g1_inf, g2_inf, lines, n, offs, k, ws, out,
+        hipLaunchKernelGGL(k_pairing_product, grid_for(k, PAIR_BLOCK), dim3(PAIR_BLOCK), 0, ctx->stream, g1, g1_inf, g2_inf, lines, n, offs, k, ws, out,
                            is_one);
     }
     CZK_HIP(ctx, hipGetLastError());
@@ -282,7 +249,7 @@ static int pairing_products_device(czk_ctx* ctx, CallBufs& cb, const u64* g1, co
 // the KZG10 verifier's entry (kzg.hip)
 int pairing_is_one_device(czk_ctx* ctx, const u64* g1, const uint8_t* g1_inf, const u64* g2, const uint8_t* g2_inf, const size_t* offs_host, size_t k,
                           uint8_t* is_one) {
-    CallBufs cb(ctx);
+    CallMem cb(ctx, "pairing workspace");
     return pairing_products_device(ctx, cb, g1, g1_inf, g2, g2_inf, offs_host, k, nullptr, is_one);
 }
 
@@ -290,23 +257,19 @@ static int pairing_products(czk_ctx* ctx, const uint64_t* g1, const uint8_t* g1_
                             const size_t* offs, size_t k, uint64_t* out, uint8_t* out_is_one, int mem) {
     const size_t n = offs[k];
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    CallBufs cb(ctx);
+    CallMem cb(ctx, "pairing workspace");
     const u64 *dg1, *dg2;
     const uint8_t *dg1i, *dg2i;
     CZK_TRY(cb.in(g1, n * 96, mem, &dg1));
     CZK_TRY(cb.in(g2, n * 192, mem, &dg2));
     CZK_TRY(cb.in(g1_inf, n, mem, &dg1i));
     CZK_TRY(cb.in(g2_inf, n, mem, &dg2i));
-    u64* dout = mem == CZK_MEM_DEVICE ? out : nullptr;
-    uint8_t* done = mem == CZK_MEM_DEVICE ? out_is_one : nullptr;
-    if (mem == CZK_MEM_HOST && out) CZK_TRY(cb.get(&dout, k * 576));
-    if (mem == CZK_MEM_HOST && out_is_one) CZK_TRY(cb.get(&done, k));
-    CZK_TRY(pairing_products_device(ctx, cb, dg1, dg1i, dg2, dg2i, offs, k, dout, done));
-    if (mem == CZK_MEM_HOST) {
-        if (out) CZK_HIP(ctx, hipMemcpy(out, dout, k * 576, hipMemcpyDeviceToHost));
-        if (out_is_one) CZK_HIP(ctx, hipMemcpy(out_is_one, done, k, hipMemcpyDeviceToHost));
-    }
-    return CZK_OK;
+    CallOut so(ctx), sone(ctx);   // (either may be null: the kernel then leaves it out)
+    if (out) CZK_TRY(so.open(out, k * 576, mem, &cb));
+    if (out_is_one) CZK_TRY(sone.open(out_is_one, k, mem, &cb));
+    CZK_TRY(pairing_products_device(ctx, cb, dg1, dg1i, dg2, dg2i, offs, k, so.words(), sone.flags()));
+    CZK_TRY(so.close());
+    return sone.close();
 }
 
 }  // namespace czk
@@ -325,7 +288,7 @@ struct czk_groth16_pvk {
 extern "C" int czk_pairing(czk_ctx* ctx, const uint64_t* g1, const uint8_t* g1_inf, const uint64_t* g2, const uint8_t* g2_inf, size_t n, uint64_t* out,
                            int mem) {
     if (!ctx || (n && (!g1 || !g2 || !out))) return ctx ? set_err(ctx, CZK_ERR_ARG, "null pairing argument") : CZK_ERR_ARG;
-    if (!valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
+    CZK_TRY(check_mem(ctx, mem));
     if (!n) return CZK_OK;
     std::vector<size_t> offs(n + 1);
     for (size_t i = 0; i <= n; i++) offs[i] = i;
@@ -335,12 +298,11 @@ extern "C" int czk_pairing(czk_ctx* ctx, const uint64_t* g1, const uint8_t* g1_i
 extern "C" int czk_pairing_product(czk_ctx* ctx, const uint64_t* g1, const uint8_t* g1_inf, const uint64_t* g2, const uint8_t* g2_inf,
                                    const size_t* offsets, size_t k, uint64_t* out, uint8_t* out_is_one, int mem) {
     if (!ctx || (k && !offsets)) return ctx ? set_err(ctx, CZK_ERR_ARG, "null pairing_product argument") : CZK_ERR_ARG;
-    if (!valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
+    CZK_TRY(check_mem(ctx, mem));
     if (!k) return CZK_OK;
-    if (offsets[0] != 0) return set_err(ctx, CZK_ERR_ARG, "offsets[0] must be 0");
-    for (size_t j = 0; j < k; j++)
-        if (offsets[j + 1] < offsets[j]) return set_err(ctx, CZK_ERR_ARG, "offsets must be non-decreasing");
-    if (offsets[k] && (!g1 || !g2)) return set_err(ctx, CZK_ERR_ARG, "null points");
+    size_t n;
+    CZK_TRY(check_offsets(ctx, offsets, k, &n));
+    if (n && (!g1 || !g2)) return set_err(ctx, CZK_ERR_ARG, "null points");
     return pairing_products(ctx, g1, g1_inf, g2, g2_inf, offsets, k, out, out_is_one, mem);
 }
 
@@ -383,7 +345,7 @@ extern "C" int czk_groth16_pvk_create(czk_ctx* ctx, const uint64_t* alpha_g1, co
         }
         std::vector<uint8_t> inf(n_gamma_abc, 0);
         if (gamma_abc_inf) inf.assign(gamma_abc_inf, gamma_abc_inf + n_gamma_abc);
-        CallBufs cb(ctx);
+        CallMem cb(ctx, "pairing workspace");
         u64* dneg = nullptr;
         rc = cb.get(&dneg, sizeof(neg));
         if (rc == CZK_OK && (hipMemcpyAsync(dneg, neg, sizeof(neg), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
@@ -416,12 +378,12 @@ extern "C" int czk_groth16_verify(czk_ctx* ctx, const czk_groth16_pvk* pvk, cons
                                   const uint8_t* inf, const uint64_t* public_inputs, size_t m, size_t k, uint8_t* out_ok, int mem) {
     if (!ctx || !pvk) return ctx ? set_err(ctx, CZK_ERR_ARG, "null verifying key") : CZK_ERR_ARG;
     if (m + 1 != pvk->n_gamma_abc) return set_err(ctx, CZK_ERR_ARG, "MalformedVerifyingKey");   // verifier.rs:28-30
-    if (!valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
-    if (pvk->device != ctx->device) return set_err(ctx, CZK_ERR_ARG, "verifying key lives on another device");
+    CZK_TRY(check_mem(ctx, mem));
+    CZK_TRY(check_device(ctx, pvk->device, "verifying key lives on another device"));
     if (!k) return CZK_OK;
     if (!a || !b || !c || !out_ok || (m && !public_inputs)) return set_err(ctx, CZK_ERR_ARG, "null proof argument");
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    CallBufs cb(ctx);
+    CallMem cb(ctx, "pairing workspace");
     const u64 *da, *db, *dc, *dx;
     const uint8_t* dinf;
     CZK_TRY(cb.in(a, k * 96, mem, &da));
@@ -430,30 +392,30 @@ extern "C" int czk_groth16_verify(czk_ctx* ctx, const czk_groth16_pvk* pvk, cons
     CZK_TRY(cb.in(inf, k * 3, mem, &dinf));
     CZK_TRY(cb.in(m ? public_inputs : nullptr, k * m * 32, mem, &dx));
     u64 *lines, *gic, *ws;
-    uint8_t *gic_inf, *dok = mem == CZK_MEM_DEVICE ? out_ok : nullptr;
+    uint8_t* gic_inf;
+    CallOut sok(ctx);
     CZK_TRY(cb.get(&lines, k * LINE_WORDS * 8));
     CZK_TRY(cb.get(&gic, k * 96));
     CZK_TRY(cb.get(&gic_inf, k));
     CZK_TRY(cb.get(&ws, k * 216 * 8));
-    if (!dok) CZK_TRY(cb.get(&dok, k));
+    CZK_TRY(sok.open(out_ok, k, mem, &cb));
     // B's infinity flag is column 1 of inf: prepare every B (an infinite B's lines are never read)
     {
         ProfScope ps(ctx, "pairing_g2_prepare", ctx->stream);
-        hipLaunchKernelGGL(k_g2_prepare, dim3(blocks(k)), dim3(PAIR_BLOCK), 0, ctx->stream, db, (const uint8_t*)nullptr, k, lines);
+        hipLaunchKernelGGL(k_g2_prepare, grid_for(k, PAIR_BLOCK), dim3(PAIR_BLOCK), 0, ctx->stream, db, (const uint8_t*)nullptr, k, lines);
     }
     {
         ProfScope ps(ctx, "groth16_gic", ctx->stream);
-        hipLaunchKernelGGL(k_groth16_gic, dim3(blocks(k)), dim3(PAIR_BLOCK), 0, ctx->stream, (const u64*)pvk->gabc, (const uint8_t*)pvk->gabc_inf, dx,
+        hipLaunchKernelGGL(k_groth16_gic, grid_for(k, PAIR_BLOCK), dim3(PAIR_BLOCK), 0, ctx->stream, (const u64*)pvk->gabc, (const uint8_t*)pvk->gabc_inf, dx,
                            m, k, gic, gic_inf);
     }
     {
         ProfScope ps(ctx, "groth16_check", ctx->stream);
-        hipLaunchKernelGGL(k_groth16_check, dim3(blocks(k)), dim3(PAIR_BLOCK), 0, ctx->stream, da, dc, dinf, (const u64*)lines, (const u64*)gic,
+        hipLaunchKernelGGL(k_groth16_check, grid_for(k, PAIR_BLOCK), dim3(PAIR_BLOCK), 0, ctx->stream, da, dc, dinf, (const u64*)lines, (const u64*)gic,
                            (const uint8_t*)gic_inf, (const u64*)pvk->lines, (const u64*)(pvk->lines + 1), (size_t)2,
-                           (const u64*)pvk->alpha_beta, k, ws, dok);
+                           (const u64*)pvk->alpha_beta, k, ws, sok.flags());
     }
     CZK_HIP(ctx, hipGetLastError());
     CZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (mem == CZK_MEM_HOST) CZK_HIP(ctx, hipMemcpy(out_ok, dok, k, hipMemcpyDeviceToHost));
-    return CZK_OK;
+    return sok.close();
 }

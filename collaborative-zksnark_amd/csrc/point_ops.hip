@@ -10,7 +10,7 @@
 // ONE batched normalisation per launch (msm_bases.hip's k_batch_to_affine through launch_batch_to_affine, as fixed_base.hip) writes the affine results:
 // infinity is flag 1 with the coordinates (0, 1).
 // All arithmetic is the 32-bit-limb integer VALU code of field.h / curve.h, with the Montgomery multiply out of line (-DCZK_NOINLINE_MUL).
-#include "czk_internal.h"
+#include "call.h"
 
 namespace czk {
 
@@ -86,172 +86,101 @@ __global__ __launch_bounds__(128) void k_points_sum(const u64* pts, const uint8_
     if (lane == 0 && seg < k) jac_store<F>(out_jac + (size_t)JW * seg, acc);
 }
 
-static unsigned blocks128(size_t n) { return (unsigned)((n + 127) / 128); }
-
-// workspace of one launch: n Jacobian results + the normalisation's running products
-struct PointWs {
-    czk_ctx* ctx;
-    DeviceBuf buf;
-    explicit PointWs(czk_ctx* c) : ctx(c) {}
-    ~PointWs() { stage_give(ctx, buf); }   // (re-use is ordered: every later user enqueues on the same stream)
-    int take(int group, size_t n, u64** jac, u64** scr) {
-        const size_t jw = group == CZK_G1 ? 18 : 36, fw = group == CZK_G1 ? 6 : 12;
-        CZK_TRY(stage_take(ctx, n * (jw + fw) * 8, &buf));
-        *jac = (u64*)buf.p;
-        *scr = *jac + n * jw;
-        return CZK_OK;
-    }
-};
-
-static int launched(czk_ctx* ctx, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, CZK_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return CZK_OK;
-}
-
 int points_add_device(czk_ctx* ctx, int group, const u64* a, const uint8_t* a_inf, size_t a_stride, const u64* b, const uint8_t* b_inf, size_t b_stride,
                       size_t n, int negate_b, u64* out, uint8_t* out_inf) {
     if (!n) return CZK_OK;
-    PointWs ws(ctx);
-    u64 *jac, *scr;
-    CZK_TRY(ws.take(group, n, &jac, &scr));
-    {
-        ProfScope ps(ctx, "points_add");
-        if (group == CZK_G1)
-            hipLaunchKernelGGL(k_points_add<Fq>, dim3(blocks128(n)), dim3(128), 0, ctx->stream, a, a_inf, a_stride, b, b_inf, b_stride, n, negate_b, jac);
-        else
-            hipLaunchKernelGGL(k_points_add<Fq2>, dim3(blocks128(n)), dim3(128), 0, ctx->stream, a, a_inf, a_stride, b, b_inf, b_stride, n, negate_b, jac);
-        launch_batch_to_affine(ctx->stream, group, jac, n, scr, out, out_inf);
-    }
-    return launched(ctx, "points_add");
+    return launch_to_affine(ctx, "points_add", "points_add", group, n, out, out_inf, [&](auto tag, u64* jac) {
+        hipLaunchKernelGGL(k_points_add<typename decltype(tag)::type>, grid_for(n), dim3(128), 0, ctx->stream, a, a_inf, a_stride, b, b_inf, b_stride, n,
+                           negate_b, jac);
+    });
 }
 
 int points_mul_device(czk_ctx* ctx, int group, const u64* pts, const uint8_t* inf, size_t stride, const u64* scalars, size_t n, int scalar_form, u64* out,
                       uint8_t* out_inf) {
     if (!n) return CZK_OK;
-    PointWs ws(ctx);
-    u64 *jac, *scr;
-    CZK_TRY(ws.take(group, n, &jac, &scr));
     const int mont = scalar_form == CZK_SCALAR_MONTGOMERY ? 1 : 0;
-    {
-        ProfScope ps(ctx, "points_mul");
-        if (group == CZK_G1)
-            hipLaunchKernelGGL(k_points_mul<Fq>, dim3(blocks128(n)), dim3(128), 0, ctx->stream, pts, inf, stride, scalars, n, mont, jac);
-        else
-            hipLaunchKernelGGL(k_points_mul<Fq2>, dim3(blocks128(n)), dim3(128), 0, ctx->stream, pts, inf, stride, scalars, n, mont, jac);
-        launch_batch_to_affine(ctx->stream, group, jac, n, scr, out, out_inf);
-    }
-    return launched(ctx, "points_mul");
+    return launch_to_affine(ctx, "points_mul", "points_mul", group, n, out, out_inf, [&](auto tag, u64* jac) {
+        hipLaunchKernelGGL(k_points_mul<typename decltype(tag)::type>, grid_for(n), dim3(128), 0, ctx->stream, pts, inf, stride, scalars, n, mont, jac);
+    });
 }
 
 // offs_host: k + 1 offsets, checked by the caller; they travel through the context's pinned transfer buffer, so the call only enqueues
 int points_sum_device(czk_ctx* ctx, int group, const u64* pts, const uint8_t* inf, const size_t* offs_host, size_t k, u64* out, uint8_t* out_inf) {
     if (!k) return CZK_OK;
-    PointWs ws(ctx);
-    u64 *jac, *scr;
-    CZK_TRY(ws.take(group, k, &jac, &scr));
-    DeviceBuf ob;
-    CZK_TRY(stage_take(ctx, (k + 1) * sizeof(size_t), &ob));
-    int rc = upload_pageable(ctx, ob.p, offs_host, (k + 1) * sizeof(size_t));
-    if (rc == CZK_OK) {
-        ProfScope ps(ctx, "points_sum");
-        const unsigned grid = (unsigned)((k + 1) / 2);
-        if (group == CZK_G1)
-            hipLaunchKernelGGL(k_points_sum<Fq>, dim3(grid), dim3(128), 0, ctx->stream, pts, inf, (const size_t*)ob.p, k, jac);
-        else
-            hipLaunchKernelGGL(k_points_sum<Fq2>, dim3(grid), dim3(128), 0, ctx->stream, pts, inf, (const size_t*)ob.p, k, jac);
-        launch_batch_to_affine(ctx->stream, group, jac, k, scr, out, out_inf);
-    }
+    DeviceBuf ws, ob;   // (the workspace first, then the offsets: the order the pool has always been asked in)
+    CZK_TRY(stage_take(ctx, affine_ws_bytes(group, k), &ws));
+    int rc = stage_take(ctx, (k + 1) * sizeof(size_t), &ob);
+    if (rc == CZK_OK) rc = upload_pageable(ctx, ob.p, offs_host, (k + 1) * sizeof(size_t));
+    if (rc == CZK_OK)
+        rc = launch_to_affine(ctx, "points_sum", "points_sum", group, k, out, out_inf, [&](auto tag, u64* jac) {
+            hipLaunchKernelGGL(k_points_sum<typename decltype(tag)::type>, grid_for(k, 2), dim3(128), 0, ctx->stream, pts, inf, (const size_t*)ob.p, k, jac);
+        }, &ws);
     stage_give(ctx, ob);
-    return rc == CZK_OK ? launched(ctx, "points_sum") : rc;
-}
-
-// Host-memory callers: every input staged into HBM, the results copied back (blocking); device-memory callers: used in place.
-struct PointOut {
-    Staged pts, inf;
-    explicit PointOut(czk_ctx* ctx) : pts{ctx}, inf{ctx} {}
-    // the normalisation always writes flags: a caller that takes none gets them into scratch
-    int open(uint64_t* out, uint8_t* out_inf, size_t n, size_t aw, int mem) {
-        CZK_TRY(pts.to_device(mem == CZK_MEM_HOST ? nullptr : out, n * aw * 8, mem));
-        const bool in_place = mem == CZK_MEM_DEVICE && out_inf;
-        return inf.to_device(in_place ? out_inf : nullptr, n, in_place ? CZK_MEM_DEVICE : CZK_MEM_HOST);
-    }
-    int close(czk_ctx* ctx, uint64_t* out, uint8_t* out_inf, size_t n, size_t aw, int mem) {
-        if (mem != CZK_MEM_HOST) return CZK_OK;
-        if (out_inf) CZK_HIP(ctx, hipMemcpyAsync(out_inf, inf.dev, n, hipMemcpyDeviceToHost, ctx->stream));
-        return pts.to_host(out, n * aw * 8);
-    }
-};
-
-static int check_common(czk_ctx* ctx, int group, int mem) {
-    if (group != CZK_G1 && group != CZK_G2) return set_err(ctx, CZK_ERR_ARG, "group must be CZK_G1 or CZK_G2");
-    if (!valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
-    return CZK_OK;
+    stage_give(ctx, ws);
+    return rc;
 }
 
 }  // namespace czk
 
 using namespace czk;
 
+// Host-memory callers: every input staged into HBM, the results copied back (blocking); device-memory callers: used in place.
 extern "C" int czk_points_add(czk_ctx* ctx, int group, const uint64_t* a, const uint8_t* a_inf, const uint64_t* b, const uint8_t* b_inf, size_t n,
                               int negate_b, uint64_t* out, uint8_t* out_inf, int mem) {
     if (!ctx) return CZK_ERR_ARG;
-    CZK_TRY(check_common(ctx, group, mem));
+    CZK_TRY(check_group_mem(ctx, group, mem));
     if (!n) return CZK_OK;
     if (!a || !b || !out) return set_err(ctx, CZK_ERR_ARG, "null points_add buffer");
     CZK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t aw = group == CZK_G1 ? 12 : 24;
     Staged sa{ctx}, sai{ctx}, sb{ctx}, sbi{ctx};
-    PointOut so(ctx);
+    AffineOut so(ctx);
     CZK_TRY(sa.to_device(a, n * aw * 8, mem));
     CZK_TRY(sb.to_device(b, n * aw * 8, mem));
     if (a_inf) CZK_TRY(sai.to_device(a_inf, n, mem));
     if (b_inf) CZK_TRY(sbi.to_device(b_inf, n, mem));
-    CZK_TRY(so.open(out, out_inf, n, aw, mem));
+    CZK_TRY(so.open(group, out, out_inf, n, mem));
     CZK_TRY(points_add_device(ctx, group, (const u64*)sa.dev, (const uint8_t*)sai.dev, 1, (const u64*)sb.dev, (const uint8_t*)sbi.dev, 1, n, negate_b ? 1 : 0,
-                              (u64*)so.pts.dev, (uint8_t*)so.inf.dev));
-    return so.close(ctx, out, out_inf, n, aw, mem);
+                              so.pts.words(), so.inf.flags()));
+    return so.close();
 }
 
 extern "C" int czk_points_mul(czk_ctx* ctx, int group, const uint64_t* pts, const uint8_t* inf, size_t pts_stride, const uint64_t* scalars, size_t n,
                               int scalar_form, uint64_t* out, uint8_t* out_inf, int mem) {
     if (!ctx) return CZK_ERR_ARG;
-    CZK_TRY(check_common(ctx, group, mem));
+    CZK_TRY(check_group_mem(ctx, group, mem));
     if (pts_stride > 1) return set_err(ctx, CZK_ERR_ARG, "pts_stride must be 1, or 0 for one point");
-    if (scalar_form != CZK_SCALAR_CANONICAL && scalar_form != CZK_SCALAR_MONTGOMERY) return set_err(ctx, CZK_ERR_ARG, "bad scalar_form");
+    CZK_TRY(check_scalar_form(ctx, scalar_form));
     if (!n) return CZK_OK;
     if (!pts || !scalars || !out) return set_err(ctx, CZK_ERR_ARG, "null points_mul buffer");
     CZK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t aw = group == CZK_G1 ? 12 : 24, np = pts_stride ? n : 1;
     Staged sp{ctx}, si{ctx}, sk{ctx};
-    PointOut so(ctx);
+    AffineOut so(ctx);
     CZK_TRY(sp.to_device(pts, np * aw * 8, mem));
     if (inf) CZK_TRY(si.to_device(inf, np, mem));
     CZK_TRY(sk.to_device(scalars, n * 32, mem));
-    CZK_TRY(so.open(out, out_inf, n, aw, mem));
-    CZK_TRY(points_mul_device(ctx, group, (const u64*)sp.dev, (const uint8_t*)si.dev, pts_stride, (const u64*)sk.dev, n, scalar_form, (u64*)so.pts.dev,
-                              (uint8_t*)so.inf.dev));
-    return so.close(ctx, out, out_inf, n, aw, mem);
+    CZK_TRY(so.open(group, out, out_inf, n, mem));
+    CZK_TRY(points_mul_device(ctx, group, (const u64*)sp.dev, (const uint8_t*)si.dev, pts_stride, (const u64*)sk.dev, n, scalar_form, so.pts.words(),
+                              so.inf.flags()));
+    return so.close();
 }
 
 extern "C" int czk_points_sum(czk_ctx* ctx, int group, const uint64_t* pts, const uint8_t* inf, const size_t* offsets, size_t k, uint64_t* out,
                               uint8_t* out_inf, int mem) {
     if (!ctx) return CZK_ERR_ARG;
-    CZK_TRY(check_common(ctx, group, mem));
+    CZK_TRY(check_group_mem(ctx, group, mem));
     if (!k) return CZK_OK;
     if (!offsets || !out) return set_err(ctx, CZK_ERR_ARG, "null points_sum buffer");
-    if (offsets[0] != 0) return set_err(ctx, CZK_ERR_ARG, "offsets[0] must be 0");
-    for (size_t j = 0; j < k; j++)
-        if (offsets[j + 1] < offsets[j]) return set_err(ctx, CZK_ERR_ARG, "offsets must be non-decreasing");
-    const size_t n = offsets[k];
+    size_t n;
+    CZK_TRY(check_offsets(ctx, offsets, k, &n));
     if (n && !pts) return set_err(ctx, CZK_ERR_ARG, "null points");
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t aw = group == CZK_G1 ? 12 : 24;
     Staged sp{ctx}, si{ctx};
-    PointOut so(ctx);
-    CZK_TRY(sp.to_device(pts, n * aw * 8, mem));
+    AffineOut so(ctx);
+    CZK_TRY(sp.to_device(pts, n * (group == CZK_G1 ? 96 : 192), mem));
     if (inf) CZK_TRY(si.to_device(inf, n, mem));
-    CZK_TRY(so.open(out, out_inf, k, aw, mem));
-    CZK_TRY(points_sum_device(ctx, group, (const u64*)sp.dev, (const uint8_t*)si.dev, offsets, k, (u64*)so.pts.dev, (uint8_t*)so.inf.dev));
-    return so.close(ctx, out, out_inf, k, aw, mem);
+    CZK_TRY(so.open(group, out, out_inf, k, mem));
+    CZK_TRY(points_sum_device(ctx, group, (const u64*)sp.dev, (const uint8_t*)si.dev, offsets, k, so.pts.words(), so.inf.flags()));
+    return so.close();
 }
