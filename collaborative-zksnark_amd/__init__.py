@@ -17,3 +17,4 @@ from . import keygen  # noqa: F401
 from . import keyio  # noqa: F401
 from . import kzg  # noqa: F401
 from . import marlin  # noqa: F401
+from . import plonk  # noqa: F401

@@ -519,6 +519,38 @@ class Context:
                                               _ptr(out if k else None), C.c_int(mem)))
         return out
 
+    def plonk_layout(self, succ, n_gates: int, n_prods: int, w_evals=None, s_evals=None, mem=CZK_MEM_HOST):
+        """CircuitLayout::from_circuit up to the evaluations of the two index polynomials (czk_plonk_layout): w_evals[i] = w^succ[i] over the 3 n_gates
+        wire slots, s_evals = n_prods zeros then ones.  Host mode takes succ as a numpy array (checked to be a permutation) and returns (w_evals
+        (3 n_gates, 4), s_evals (n_gates, 4)); device mode: pointers, with w_evals / s_evals device buffers."""
+        if mem == CZK_MEM_HOST:
+            succ = np.ascontiguousarray(succ, np.uint32).reshape(-1)
+            sized = n_gates > 0 and not n_gates & (n_gates - 1) and 3 * n_gates < 1 << 32    # otherwise the library refuses before it reads or writes
+            if sized and succ.size != 3 * n_gates:
+                raise ValueError("succ must hold 3 n_gates slot indices")
+            w_evals = np.zeros((3 * n_gates if sized else 1, 4), dtype=np.uint64)
+            s_evals = np.zeros((n_gates if sized else 1, 4), dtype=np.uint64)
+        self._ck(self._L.czk_plonk_layout(self._h, _ptr(succ), C.c_size_t(n_gates), C.c_size_t(n_prods), _ptr(w_evals), _ptr(s_evals), C.c_int(mem)))
+        return w_evals, s_evals
+
+    def fr_gather(self, src, index, lanes: int = 1, src_len=None, src_stride=None, n=None, out=None, out_stride=None, mem=CZK_MEM_HOST):
+        """out[l][i] = src[l][index[i]] on every lane (czk_fr_gather).  Host mode: src (lanes, src_stride, 4) and index as numpy arrays, src_len
+        (default src_stride) valid elements per lane, `out` an optional (lanes, out_stride, 4) array whose elements past n stay; returns out.  Device
+        mode: pointers with src_len, src_stride, n and out_stride given."""
+        if mem == CZK_MEM_HOST:
+            src = np.ascontiguousarray(src, np.uint64).reshape(lanes, -1, 4) if lanes else np.zeros((0, 0, 4), dtype=np.uint64)
+            index = np.ascontiguousarray(index, np.uint32).reshape(-1)
+            src_stride, n = src.shape[1], index.size
+            src_len = src_stride if src_len is None else src_len
+            assert src_len <= src_stride
+            if out is None:
+                out = np.zeros((lanes, n, 4), dtype=np.uint64)
+            assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape[0] == lanes and (not lanes or out.shape[1] >= n)
+            out_stride = out.shape[1] if lanes else n
+        self._ck(self._L.czk_fr_gather(self._h, _ptr(src if lanes and n else None), C.c_size_t(src_len), C.c_size_t(src_stride), C.c_size_t(lanes),
+                                     _ptr(index if lanes and n else None), C.c_size_t(n), _ptr(out if lanes and n else None), C.c_size_t(out_stride), C.c_int(mem)))
+        return out
+
     def poly_div_linear(self, coeffs, z, lanes: int = 1, n=None, quotient=None, remainder=None, mem=CZK_MEM_HOST):
         """coeffs / (X - z) per lane; host mode returns (quotient (lanes, n-1, 4), remainder (lanes, 4))."""
         z = np.ascontiguousarray(z, np.uint64).reshape(4)

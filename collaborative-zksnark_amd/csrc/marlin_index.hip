@@ -7,28 +7,12 @@
 // by u_H(e, e) = |H| e^(|H| - 1) through a map and a batch inversion (:169-172, :195-204); on H that is e / |H|, so no inversion is needed here.
 // Slots past the last entry hold row = col = row_col = 1, val = 0 (:207-211).
 //
-// Domain elements: four tables of 256 powers, T_j[b] = w^(b 2^(8 j)), built on the device per call (1024 field elements); w^e is the product of one entry
+// Domain elements (pow_tables.h): four tables of 256 powers, T_j[b] = w^(b 2^(8 j)), built on the device per call (1024 field elements); w^e is the product of one entry
 // per byte of e -- ceil(log|H| / 8) - 1 multiplications -- so nothing of size |H| is built or crosses from the host.  One thread per slot; the row of a
 // slot is found by a binary search of row_ptr.
-#include "czk_internal.h"
+#include "pow_tables.h"
 
 namespace czk {
-
-struct MarlinRoots {
-    Fr w[4];   // w^(2^(8 j))
-};
-
-__global__ __launch_bounds__(256) void k_marlin_pow_tables(u64* tab, MarlinRoots roots) {   // 4 blocks of 256
-    const unsigned j = blockIdx.x, b = threadIdx.x;
-    fp_store<FrParams>(tab + 4 * (size_t)(256 * j + b), fp_pow_u64(roots.w[j], (u64)b));
-}
-
-// w^e for e < 2^log_h <= 2^32, nb = ceil(log_h / 8) tables in use (e is masked by the caller: every byte index stays inside a table)
-__device__ __forceinline__ Fr marlin_domain_element(const u64* tab, u32 e, unsigned nb) {
-    Fr v = fp_load<FrParams>(tab + 4 * (size_t)(e & 255u));
-    for (unsigned j = 1; j < nb; j++) v = fp_mul(v, fp_load<FrParams>(tab + 4 * (size_t)(256 * j + ((e >> (8 * j)) & 255u))));
-    return v;
-}
 
 // out: row | col | val | row_col, k Fr each.  The kernel reads nothing outside row_ptr[0..m], col_idx[0..nnz), coeff[0..nnz) and the tables whatever those
 // arrays hold: the search ends on an index below m for any row_ptr, and exponents are reduced modulo |H| before they index a table.
@@ -97,12 +81,7 @@ extern "C" int czk_marlin_arithmetize(czk_ctx* ctx, const uint64_t* row_ptr, con
     CZK_HIP(ctx, hipSetDevice(ctx->device));
     DomainTables* d = nullptr;
     CZK_TRY(get_domain(ctx, log_h, &d));
-    MarlinRoots roots;
-    roots.w[0] = d->group_gen;
-    for (int j = 1; j < 4; j++) {
-        roots.w[j] = roots.w[j - 1];
-        for (int s = 0; s < 8; s++) roots.w[j] = fp_sqr(roots.w[j]);
-    }
+    const MarlinRoots roots = pow_table_roots(d->group_gen);
     Staged sr{ctx}, sc{ctx}, sv{ctx}, so{ctx}, tab{ctx};
     CZK_TRY(sr.to_device(row_ptr, (m + 1) * 8, mem));
     if (nnz) {

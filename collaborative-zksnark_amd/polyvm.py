@@ -645,8 +645,8 @@ def plonk_inputs(B: Backend, n_gates: int, seed: int = 0x9107) -> dict:
 
 
 def plonk_prove(B: Backend, inp: dict) -> dict:
-    """Local compute of `Prover::prove` (mpc-plonk/src/lib.rs:430-448) on plonk_inputs.  Returns every commitment and opening in
-    the reference's order."""
+    """Local compute of `Prover::prove` (mpc-plonk/src/lib.rs:430-448) on plonk_inputs, or on plonk.prover_inputs for a circuit of the caller's
+    (then with inp["public_points"], any number of public wires).  Returns every commitment and opening in the reference's order."""
     G = inp["n_gates"]
     W = 3 * G
     w = B.root_of_unity(W)                                                     # domains.wires.group_gen (mixed radix)
@@ -662,8 +662,15 @@ def plonk_prove(B: Backend, inp: dict) -> dict:
         out[label]["of"] = of          # label of the opened polynomial's commitment (None: an index polynomial, committed at setup)
 
     commit("p", p)                                                             # :434-441
-    # prove_public (:259-292) with one public wire: v = p(x_pub) constant, z = X - x_pub, q = (p - v) / z
-    q_pub = B.quotient(p, w)
+    # prove_public (:259-292): v = the interpolation of p through the public wires x_1 .. x_k, z = prod (X - x_i), q = the quotient of (p - v) / z.
+    # Dividing by the linear factors one after another and dropping each remainder gives the quotient by their product: p = q_1 (X - x_1) + r_1 and
+    # q_1 = q_2 (X - x_2) + r_2 make p = q_2 (X - x_1)(X - x_2) + [r_2 (X - x_1) + r_1] with a bracket of lower degree than the product, and so on.
+    # deg v < k = deg z, so (p - v) / z has the quotient of p / z: v never has to be formed.  Every step is linear in p with public divisors, so it
+    # holds lane by lane on SPDZ, additive and GSZ shares alike.  inp["public_points"]: the x_i as canonical integers (plonk.layout); absent, it is
+    # the one public wire at w^1 of plonk_inputs and tests/polyiop_real.py.
+    q_pub = p
+    for x_pub in inp.get("public_points", [w]):
+        q_pub = B.quotient(q_pub, x_pub)
     commit("pub_q", q_pub)
     B.transcript_point()
     x = challenge("plonk.public.x")
@@ -734,6 +741,8 @@ def _padded_add(B, a, b):
 def plonk_commit_sizes(n_gates: int):
     """lengths of the polynomials plonk_prove commits (for GpuBackend.prepare): p / l1 / t / q_up / l2_q (3 G), the public quotient and the opening
     witnesses (one shorter), gates_q (6 G - 2), the selector's witness (G - 1)"""
+    # (k > 1 public wires: the public quotient has W - k coefficients and its witness W - k - 1 -- shorter than W - 1, so they run on a table set
+    # these lengths have prepared; nothing longer is committed)
     G, W = n_gates, 3 * n_gates
     return [W, W - 1, 6 * G - 2, 6 * G - 3, G - 1]
 

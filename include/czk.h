@@ -386,6 +386,22 @@ int czk_r1cs_matvec(czk_ctx* ctx, const czk_r1cs_matrix* a, const uint64_t* z, s
  * arrays, so their contents are the caller's to check; slots of malformed entries are unspecified, and nothing outside the arrays is accessed. */
 int czk_marlin_arithmetize(czk_ctx* ctx, const uint64_t* row_ptr, const uint32_t* col_idx, const uint64_t* coeff, size_t m, size_t nnz,
                            unsigned log_h, unsigned log_x, size_t n_instance, size_t k, uint64_t* out, int mem);
+/* CircuitLayout::from_circuit (mpc-plonk/src/relations/flat.rs:35-137) up to the evaluation vectors of the two index polynomials, for a circuit of
+ * n_gates gates (a power of two) of which the first n_prods are products (:40-46).  W = 3 n_gates wire slots (in0, in1, out per gate), w =
+ * get_root_of_unity(W) of the mixed-radix domain (:282-300; the group_gen of czk_mixed_domain_constants(W)).  succ: W slot indices, the wiring
+ * permutation -- each slot of a variable names the variable's next slot, the last the first (:75-80).
+ *   w_evals[i] = w^succ[i] (W Fr),   s_evals[j] = 0 for j < n_prods, 1 for n_prods <= j < n_gates (n_gates Fr).
+ * CZK_ERR_SIZE for n_gates zero or not a power of two, 3 n_gates >= 2^32, a size without a domain, or n_prods > n_gates.  CZK_MEM_HOST: CZK_ERR_ARG
+ * unless succ is a permutation of [0, W); the call blocks.  CZK_MEM_DEVICE: the call only enqueues on the context's stream and cannot read succ: a
+ * slot with succ[i] >= W gets the value 0 (no domain element), and nothing outside succ[0..W) is accessed whatever it holds. */
+int czk_plonk_layout(czk_ctx* ctx, const uint32_t* succ, size_t n_gates, size_t n_prods, uint64_t* w_evals, uint64_t* s_evals, int mem);
+/* out[l][i] = src[l][index[i]] for i < n on every lane l < lanes: the step p_evals[i] = vals[var] of flat.rs:91-100 over share lanes (the index
+ * array is public, the values are shares).  src: lanes x src_stride Fr of which src_len per lane are valid (src_stride >= src_len); out: lanes x
+ * out_stride Fr (out_stride >= n; elements [n, out_stride) of a lane are not written).  n = 0 or lanes = 0: CZK_OK, nothing is touched.
+ * CZK_ERR_SIZE for a stride shorter than its lane, src_len = 0 or lanes > 65535.  CZK_MEM_HOST: CZK_ERR_ARG for an index >= src_len; the call
+ * blocks.  CZK_MEM_DEVICE: the call only enqueues on the context's stream; an index >= src_len writes 0, and nothing outside the arrays is accessed. */
+int czk_fr_gather(czk_ctx* ctx, const uint64_t* src, size_t src_len, size_t src_stride, size_t lanes, const uint32_t* index, size_t n,
+                  uint64_t* out, size_t out_stride, int mem);
 /* DensePolynomial / (X - z): KZG10::compute_witness_polynomial (poly-commit/src/kzg10/mod.rs:200-224; shares divide
  * lane-wise because the divisor is public, mpc-algebra/src/share/add.rs:148-156).  coeffs: lanes x n Fr, low degree
  * first; quotient: lanes x (n-1) Fr; remainder (may be NULL): lanes Fr = p(z), which is also

@@ -690,6 +690,27 @@ inline std::vector<Fr> marlin_arithmetize(const Context& ctx, const uint64_t* ro
     return out;
 }
 
+// CircuitLayout::from_circuit (mpc-plonk/src/relations/flat.rs:35-137) up to the evaluations of the two index polynomials: w_evals[i] = w^succ[i] over the
+// 3 n_gates wire slots (w = get_root_of_unity(3 n_gates)), s_evals = n_prods zeros, then ones.  succ: the wiring permutation, 3 n_gates slot indices.
+struct PlonkLayoutEvals {
+    std::vector<Fr> w_evals, s_evals;
+};
+inline PlonkLayoutEvals plonk_layout(const Context& ctx, const std::vector<uint32_t>& succ, size_t n_gates, size_t n_prods) {
+    if (succ.size() != 3 * n_gates) throw Panic(CZK_ERR_SIZE, "plonk_layout: succ must hold 3 n_gates slot indices");
+    PlonkLayoutEvals out{std::vector<Fr>(3 * n_gates, Fr{{0, 0, 0, 0}}), std::vector<Fr>(n_gates, Fr{{0, 0, 0, 0}})};
+    ctx.check(czk_plonk_layout(ctx.raw(), succ.data(), n_gates, n_prods, n_gates ? out.w_evals[0].l : nullptr, n_gates ? out.s_evals[0].l : nullptr,
+                               CZK_MEM_HOST));
+    return out;
+}
+
+// out[i] = src[index[i]] (p_evals[i] = vals[var], flat.rs:91-100), one lane on the host
+inline std::vector<Fr> fr_gather(const Context& ctx, const std::vector<Fr>& src, const std::vector<uint32_t>& index) {
+    std::vector<Fr> out(index.size(), Fr{{0, 0, 0, 0}});
+    ctx.check(czk_fr_gather(ctx.raw(), src.empty() ? nullptr : src[0].l, src.size(), src.size(), 1, index.data(), index.size(),
+                            out.empty() ? nullptr : out[0].l, index.size(), CZK_MEM_HOST));
+    return out;
+}
+
 // mpc-snarks/src/groth/r1cs_to_qap.rs:47-113 -- the NTT / pointwise sequence of witness_map for a single prover
 // (T = Fr).  `a`, `b`, `c` are the evaluated constraint rows (a[0..N), then the instance copy; :67-83, :95-100).
 // `batch_product` is F::batch_product_in_place (:92) -- a plain product here, the Beaver protocol for shares.

@@ -141,6 +141,8 @@ extern "C" {
     pub fn czk_r1cs_matrix_release(a: *mut czk_r1cs_matrix);
     pub fn czk_r1cs_matvec(ctx: *mut czk_ctx, a: *const czk_r1cs_matrix, z: *const u64, z_stride: usize, lanes: usize, out: *mut u64, out_stride: usize, mem: c_int) -> c_int;
     pub fn czk_marlin_arithmetize(ctx: *mut czk_ctx, row_ptr: *const u64, col_idx: *const u32, coeff: *const u64, m: usize, nnz: usize, log_h: c_uint, log_x: c_uint, n_instance: usize, k: usize, out: *mut u64, mem: c_int) -> c_int;
+    pub fn czk_plonk_layout(ctx: *mut czk_ctx, succ: *const u32, n_gates: usize, n_prods: usize, w_evals: *mut u64, s_evals: *mut u64, mem: c_int) -> c_int;
+    pub fn czk_fr_gather(ctx: *mut czk_ctx, src: *const u64, src_len: usize, src_stride: usize, lanes: usize, index: *const u32, n: usize, out: *mut u64, out_stride: usize, mem: c_int) -> c_int;
     pub fn czk_poly_div_linear(ctx: *mut czk_ctx, coeffs: *const u64, n: usize, lanes: usize, z: *const u64, quotient: *mut u64, remainder: *mut u64, mem: c_int) -> c_int;
     pub fn czk_poly_evaluate(ctx: *mut czk_ctx, coeffs: *const u64, n: usize, lanes: usize, z: *const u64, values: *mut u64, mem: c_int) -> c_int;
     pub fn czk_poly_evaluate_many(ctx: *mut czk_ctx, count: usize, coeffs: *const *const u64, n: *const usize, lanes: *const usize, z: *const u64, values: *const *mut u64) -> c_int;
