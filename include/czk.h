@@ -445,7 +445,8 @@ int czk_fr_prefix_product(czk_ctx* ctx, const uint64_t* x, size_t n, uint64_t* o
  * In device memory out must not alias v. */
 int czk_fr_batch_inverse(czk_ctx* ctx, const uint64_t* v, size_t n, const uint64_t* coeff, uint64_t* out, int mem);
 
-/* Fr::into_repr / from_repr over a vector (fields/arithmetic.rs:59-81, macros.rs:443-454) -- also the wire format. */
+/* Fr::into_repr / from_repr over a vector (fields/arithmetic.rs:59-81, macros.rs:443-454) -- also the wire format.  out may alias a
+ * (conversion in place); any other overlap of the two is not allowed. */
 int czk_fr_into_repr(czk_ctx* ctx, const uint64_t* a, uint64_t* out, size_t n, int mem);
 int czk_fr_from_repr(czk_ctx* ctx, const uint64_t* a, uint64_t* out, size_t n, int mem);
 
