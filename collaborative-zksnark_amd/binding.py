@@ -903,9 +903,26 @@ class Context:
         self._ck(self._L.czk_witness_map_pre(self._h, _ptr(a_ptr), C.c_size_t(d if a_len is None else a_len), _ptr(b_ptr),
                                            C.c_size_t(d if b_len is None else b_len), C.c_uint(log_d), C.c_size_t(lanes)))
 
+    def witness_map_pre_masked(self, a_ptr, b_ptr, mask_a_ptr, mask_b_ptr, log_d, lanes, a_len=None, b_len=None):
+        """witness_map_pre with a += mask_a, b += mask_b (lanes x D each) on the transforms' last store: the factors of a Beaver product"""
+        d = 1 << log_d
+        self._ck(self._L.czk_witness_map_pre_masked(self._h, _ptr(a_ptr), C.c_size_t(d if a_len is None else a_len), _ptr(b_ptr),
+                                                  C.c_size_t(d if b_len is None else b_len), _ptr(mask_a_ptr), _ptr(mask_b_ptr), C.c_uint(log_d),
+                                                  C.c_size_t(lanes)))
+
+    def spdz_open_combine(self, a_ptr, b_ptr, tx_ptr, ty_ptr, tz_ptr, parties, king_mask, sx_ptr, oy_ptr, chk_a_ptr, chk_b_ptr, ab_ptr, n):
+        """both local opens of a Beaver product and every lane's combine in one kernel (czk_spdz_open_combine, include/czk.h); device pointers"""
+        self._ck(self._L.czk_spdz_open_combine(self._h, _ptr(a_ptr), _ptr(b_ptr), _ptr(tx_ptr), _ptr(ty_ptr), _ptr(tz_ptr), C.c_size_t(parties),
+                                             C.c_uint64(king_mask), _ptr(sx_ptr), _ptr(oy_ptr), _ptr(chk_a_ptr), _ptr(chk_b_ptr), _ptr(ab_ptr), C.c_size_t(n)))
+
     def witness_map_post(self, ab_ptr, c_ptr, log_d, lanes, c_len=None):
         self._ck(self._L.czk_witness_map_post(self._h, _ptr(ab_ptr), _ptr(c_ptr), C.c_size_t((1 << log_d) if c_len is None else c_len),
                                             C.c_uint(log_d), C.c_size_t(lanes)))
+
+    def witness_map_post_h(self, ab_ptr, c_ptr, log_d, lanes, c_len=None):
+        """witness_map_post for h alone: c is scratch (ifft(c) afterwards), one transform fewer"""
+        self._ck(self._L.czk_witness_map_post_h(self._h, _ptr(ab_ptr), _ptr(c_ptr), C.c_size_t((1 << log_d) if c_len is None else c_len),
+                                              C.c_uint(log_d), C.c_size_t(lanes)))
 
 
 class Net:

@@ -171,6 +171,8 @@ struct czk_ctx {
     int chaos_drop_wait = 0;
     bool ntt_fuse_pairs = false;     // "ntt_fuse_pairs": the witness map's ifft -> coset_fft pairs share a pass where their tiles line up (ntt.hip ifft_coset_fft_device);
                                      // measured + 0.5 % per Groth16 proof (EXPERIMENTS.md section 14), below the 1 % adoption bar: off by default
+    uint8_t witness_map_short = 7;   // "witness_map_short", a bit set: 1 = czk_witness_map_post_h transforms c once, 2 = czk_witness_map_pre_masked adds on the transforms' last store,
+                                     // 4 = czk_spdz_open_combine is one kernel; a clear bit = the same values from the kernel sequence of before (EXPERIMENTS.md section 22)
     bool ntt_gen1 = false;           // "ntt_gen1": first-generation NTT passes (ntt.hip, the small-domain kernels) for every size
     bool profiling = false;
     std::map<std::string, czk::ProfEntry> prof;
@@ -328,7 +330,10 @@ void xfer_destroy(czk_ctx* ctx);
 int upload_pageable(czk_ctx* ctx, void* dev, const void* host, size_t bytes);
 int download_pageable(czk_ctx* ctx, void* host, const void* dev, size_t bytes);
 // implemented in ntt.hip
-int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, size_t in_len, const u64* src = nullptr, size_t src_stride = 0);
+// `addend` (lanes x D canonical Fr, not the lanes being transformed) rides on the last pass's store: a coset inverse transform writes
+// (coset_ifft(data) - addend) * *scale, a forward or coset forward transform writes its output + addend (scale unused).  Same values as the pointwise kernels.
+int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, size_t in_len, const u64* src = nullptr, size_t src_stride = 0,
+               const u64* addend = nullptr, const Fr* scale = nullptr);
 // implemented in ntt_mixed.hip
 int get_mixed_domain(czk_ctx* ctx, unsigned k, MixedDomain** out);
 int ntt_mixed_device(czk_ctx* ctx, u64* data, unsigned k, size_t lanes, int kind, size_t in_len);

@@ -282,6 +282,36 @@ static unsigned grid_for(czk_ctx* ctx, size_t n) {
     return blocks ? (unsigned)blocks : 1u;
 }
 
+// The two local opens of S::batch_mul and its combine (share/field.rs:97-127, share/spdz.rs:166-185) for the layout where every party's (sh, mac) lanes are on
+// this GPU: per index the masked a = s + x and b = o + y lanes are read once, sx / oy / the two MAC-check values are written once and every lane's product share
+// z - y sx - x oy (+ sx oy on the lanes of `king_mask`) follows from registers.  The values of k_vec_op ADD / SUB per open and k_beaver per lane.
+__global__ void k_spdz_open_combine(const u64* a, const u64* b, const u64* tx, const u64* ty, const u64* tz, unsigned parties, unsigned long long king_mask, u64* sx,
+                                    u64* oy, u64* chk_a, u64* chk_b, u64* ab, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        Fr vsx = gfr_load(a, i), voy = gfr_load(b, i);                           // party 0, sh lane
+        for (unsigned p = 1; p < parties; p++) {
+            vsx = fp_add(vsx, gfr_load(a + 4 * n * (2 * p), i));
+            voy = fp_add(voy, gfr_load(b + 4 * n * (2 * p), i));
+        }
+        Fr ca = vsx, cb = voy;                                                   // mac_share * value - sum of the mac lanes, mac_share = 1
+        for (unsigned p = 0; p < parties; p++) {
+            ca = fp_sub(ca, gfr_load(a + 4 * n * (2 * p + 1), i));
+            cb = fp_sub(cb, gfr_load(b + 4 * n * (2 * p + 1), i));
+        }
+        gfr_store(sx, i, vsx);
+        gfr_store(oy, i, voy);
+        gfr_store(chk_a, i, ca);
+        gfr_store(chk_b, i, cb);
+        const Fr open = fp_mul(vsx, voy);
+        for (unsigned ln = 0; ln < 2 * parties; ln++) {
+            Fr r = fp_sub(gfr_load(tz + 4 * n * ln, i), fp_mul(gfr_load(ty + 4 * n * ln, i), vsx));
+            r = fp_sub(r, fp_mul(gfr_load(tx + 4 * n * ln, i), voy));
+            if ((king_mask >> ln) & 1ull) r = fp_add(r, open);
+            gfr_store(ab + 4 * n * ln, i, r);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // domain object (host side of Radix2EvaluationDomain::new, radix2/mod.rs:51-82)
 // ------------------------------------------------------------------------------------------------
@@ -395,8 +425,10 @@ static int ensure_tables(czk_ctx* ctx, DomainTables* d, bool need_coset_fwd, boo
 // ------------------------------------------------------------------------------------------------
 // driver
 // ------------------------------------------------------------------------------------------------
-int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, size_t in_len, const u64* src, size_t src_stride) {
+int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, size_t in_len, const u64* src, size_t src_stride, const u64* addend,
+               const Fr* scale) {
     if (kind < 0 || kind > 3) return set_err(ctx, CZK_ERR_ARG, "bad ntt kind");
+    if (addend && (kind == CZK_IFFT || (kind == CZK_COSET_IFFT && !scale))) return set_err(ctx, CZK_ERR_ARG, "ntt addend: unsupported kind");
     if (!src) {   // in place
         src = data;
         src_stride = (size_t)1 << log_d;
@@ -432,7 +464,7 @@ int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, 
     unsigned s_hi_plus1 = n;
     if (n >= NTT2_MIN_LOG && !ctx->ntt_gen1) {
         // second-generation passes (ntt_pass.hip): register-resident radix-8 / radix-4 groups, unsaturated arithmetic
-        Pass2Args b;
+        Pass2Args b{};
         b.tw = inverse ? d->twu_inv : d->twu_fwd;
         b.n = n;
         b.in_len = in_len;
@@ -447,7 +479,9 @@ int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, 
             b.first = first ? 1 : 0;
             b.prescale = (first && kind == CZK_COSET_FFT) ? d->cosetu_fwd : nullptr;
             b.posttab = (last && kind == CZK_COSET_IFFT) ? d->cosetu_inv : nullptr;
-            b.post_mode = !last ? 0 : (kind == CZK_IFFT ? 1 : (kind == CZK_COSET_IFFT ? 2 : 0));
+            b.post_mode = !last ? 0 : (kind == CZK_IFFT ? 1 : (kind == CZK_COSET_IFFT ? (addend ? 3 : 2) : (addend ? 4 : 0)));
+            b.addend = addend;
+            if (addend && scale) b.postconst2 = host_fr_to_u(*scale);
             b.in = first ? src : scratch;
             b.out = last ? data : scratch;
 #ifdef CZK_LAB
@@ -490,6 +524,12 @@ int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, 
             if (lds > ctx->lds_per_block) return set_err(ctx, CZK_ERR_HIP, "NTT last pass needs more LDS per workgroup than this device offers");
             hipLaunchKernelGGL(k_ntt_final, dim3(blocks, (unsigned)lanes), dim3(256), lds, ctx->stream, a);
         }
+        CZK_HIP(ctx, hipGetLastError());
+    }
+    if (addend) {   // first-generation passes: the addend as one pointwise kernel behind the transform
+        const size_t cnt = lanes * D;
+        if (kind == CZK_COSET_IFFT) hipLaunchKernelGGL(k_sub_scale, dim3(grid_for(ctx, cnt)), dim3(256), 0, ctx->stream, (const u64*)data, addend, *scale, data, cnt);
+        else hipLaunchKernelGGL(k_vec_op, dim3(grid_for(ctx, cnt)), dim3(256), 0, ctx->stream, (int)CZK_OP_ADD, (const u64*)data, addend, data, cnt);
         CZK_HIP(ctx, hipGetLastError());
     }
     return CZK_OK;
@@ -630,8 +670,8 @@ int czk::ntt_reserve(czk_ctx* ctx, unsigned log_d, size_t lanes) {
     CZK_TRY(get_domain(ctx, log_d, &d));
     CZK_TRY(ensure_tables(ctx, d, true, true));
     const size_t D = (size_t)1 << log_d;
-    // (twice the lanes: the fused pass of an ifft -> coset_fft pair writes a second set of scratch lanes, ifft_coset_fft_device)
-    if (log_d > 7 && lanes) CZK_TRY(ensure_buf(ctx, ctx->ntt_scratch, 2 * lanes * D * (log_d >= NTT2_MIN_LOG ? NTT2_SCRATCH_ELEM_BYTES : 32)));
+    // (twice the lanes with "ntt_fuse_pairs": the fused pass of an ifft -> coset_fft pair writes a second set of scratch lanes; set later, ifft_coset_fft_device grows the buffer)
+    if (log_d > 7 && lanes) CZK_TRY(ensure_buf(ctx, ctx->ntt_scratch, (ctx->ntt_fuse_pairs ? 2 : 1) * lanes * D * (log_d >= NTT2_MIN_LOG ? NTT2_SCRATCH_ELEM_BYTES : 32)));
     CZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CZK_OK;
 }
@@ -724,13 +764,13 @@ extern "C" int czk_fr_from_repr(czk_ctx* ctx, const uint64_t* a, uint64_t* out, 
 // data <- coset_fft(ifft(data)) per lane: the pair R1CStoQAP::witness_map applies to a, b and c (mpc-snarks/src/groth/r1cs_to_qap.rs:85-89, 102-103).  Where the
 // two transforms' pass structures line up (the stage bits split into equal groups: 2^21 = 7 + 7 + 7, also 2^12, 2^14, 2^15, 2^18) the last pass of the
 // inverse and the first pass of the forward transform run as ONE kernel (ntt_pass.hip k_ntt2_final_first): five trips through HBM instead of six, same values.
-static int ifft_coset_fft_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, size_t in_len) {
+static int ifft_coset_fft_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, size_t in_len, const u64* addend = nullptr) {
     const unsigned n = log_d;
     const unsigned m = n == 0 ? 1 : (n + 6) / 7;
     const bool fuse = ctx->ntt_fuse_pairs && !ctx->ntt_gen1 && n >= NTT2_MIN_LOG && m >= 2 && n % m == 0;   // equal groups: the two passes own the same tiles
     if (!fuse) {
         CZK_TRY(ntt_device(ctx, data, log_d, lanes, CZK_IFFT, in_len));
-        return ntt_device(ctx, data, log_d, lanes, CZK_COSET_FFT, (size_t)1 << log_d);
+        return ntt_device(ctx, data, log_d, lanes, CZK_COSET_FFT, (size_t)1 << log_d, nullptr, 0, addend);
     }
     DomainTables* d = nullptr;
     CZK_TRY(get_domain(ctx, log_d, &d));
@@ -778,6 +818,7 @@ static int ifft_coset_fft_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t
         fwd.first = 0, fwd.prescale = nullptr;
         fwd.in = sb;
         fwd.out = last ? data : sb;
+        if (last && addend) fwd.post_mode = 4, fwd.addend = addend;
         ProfScope ps(ctx, "ntt_pass");
         CZK_TRY(launch_ntt2_pass(ctx, fwd, K, last, lanes));
     }
@@ -795,17 +836,88 @@ extern "C" int czk_witness_map_pre(czk_ctx* ctx, uint64_t* a, size_t a_len, uint
     return CZK_OK;
 }
 
-extern "C" int czk_witness_map_post(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes) {
+extern "C" int czk_witness_map_pre_masked(czk_ctx* ctx, uint64_t* a, size_t a_len, uint64_t* b, size_t b_len, const uint64_t* mask_a, const uint64_t* mask_b,
+                                          unsigned log_d, size_t lanes) {
+    if (!ctx || !a || !b || !mask_a || !mask_b) return ctx ? set_err(ctx, CZK_ERR_ARG, "null witness_map argument") : CZK_ERR_ARG;
+    CZK_HIP(ctx, hipSetDevice(ctx->device));
+    if (log_d > 47) return set_err(ctx, CZK_ERR_SIZE, "domain larger than 2^TWO_ADICITY (radix2/mod.rs:61-63)");
+    const size_t D = (size_t)1 << log_d;
+    if (a_len > D || b_len > D) return set_err(ctx, CZK_ERR_SIZE, "witness_map: more evaluations than the domain holds");
+    if (!(ctx->witness_map_short & 2)) {   // the sequence of before: the transforms, then one pointwise addition per vector
+        CZK_TRY(czk_witness_map_pre(ctx, a, a_len, b, b_len, log_d, lanes));
+        const size_t n = lanes * D;
+        if (!n) return CZK_OK;
+        hipLaunchKernelGGL(k_vec_op, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, (int)CZK_OP_ADD, (const u64*)a, (const u64*)mask_a, (u64*)a, n);
+        hipLaunchKernelGGL(k_vec_op, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, (int)CZK_OP_ADD, (const u64*)b, (const u64*)mask_b, (u64*)b, n);
+        CZK_HIP(ctx, hipGetLastError());
+        return CZK_OK;
+    }
+    CZK_TRY(ifft_coset_fft_device(ctx, a, log_d, lanes, a_len, (const u64*)mask_a));
+    CZK_TRY(ifft_coset_fft_device(ctx, b, log_d, lanes, b_len, (const u64*)mask_b));
+    return CZK_OK;
+}
+
+extern "C" int czk_spdz_open_combine(czk_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, size_t parties,
+                                     uint64_t king_mask, uint64_t* sx, uint64_t* oy, uint64_t* chk_a, uint64_t* chk_b, uint64_t* ab, size_t n) {
+    if (!ctx) return CZK_ERR_ARG;
+    if (parties == 0 || parties > 32) return set_err(ctx, CZK_ERR_ARG, "spdz_open_combine: 1 to 32 parties (the king mask has one bit per lane)");
+    if (n && (!a || !b || !tx || !ty || !tz || !sx || !oy || !chk_a || !chk_b || !ab)) return set_err(ctx, CZK_ERR_ARG, "null spdz_open_combine argument");
+    if (!n) return CZK_OK;
+    CZK_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned g = grid_for(ctx, n);
+    if (!(ctx->witness_map_short & 4)) {   // the sequence of before: three pointwise kernels per open (P = 2), one combine per lane
+        auto op = [&](int o, const u64* x, const u64* y, u64* out) { hipLaunchKernelGGL(k_vec_op, dim3(g), dim3(256), 0, ctx->stream, o, x, y, out, n); };
+        const u64* src[2] = {(const u64*)a, (const u64*)b};
+        u64* val[2] = {(u64*)sx, (u64*)oy};
+        u64* chk[2] = {(u64*)chk_a, (u64*)chk_b};
+        for (int v = 0; v < 2; v++) {
+            if (parties == 1) {
+                CZK_HIP(ctx, hipMemcpyAsync(val[v], src[v], n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+            } else {
+                op(CZK_OP_ADD, src[v], src[v] + 4 * n * 2, val[v]);
+                for (size_t p = 2; p < parties; p++) op(CZK_OP_ADD, val[v], src[v] + 4 * n * 2 * p, val[v]);
+            }
+            op(CZK_OP_SUB, val[v], src[v] + 4 * n, chk[v]);
+            for (size_t p = 1; p < parties; p++) op(CZK_OP_SUB, chk[v], src[v] + 4 * n * (2 * p + 1), chk[v]);
+        }
+        for (size_t ln = 0; ln < 2 * parties; ln++)
+            hipLaunchKernelGGL(k_beaver, dim3(g), dim3(256), 0, ctx->stream, (const u64*)tx + 4 * n * ln, (const u64*)ty + 4 * n * ln, (const u64*)tz + 4 * n * ln,
+                               (const u64*)sx, (const u64*)oy, (int)((king_mask >> ln) & 1), (u64*)ab + 4 * n * ln, n);
+        CZK_HIP(ctx, hipGetLastError());
+        return CZK_OK;
+    }
+    hipLaunchKernelGGL(k_spdz_open_combine, dim3(g), dim3(256), 0, ctx->stream, (const u64*)a, (const u64*)b, (const u64*)tx, (const u64*)ty, (const u64*)tz,
+                       (unsigned)parties, (unsigned long long)king_mask, (u64*)sx, (u64*)oy, (u64*)chk_a, (u64*)chk_b, (u64*)ab, n);
+    CZK_HIP(ctx, hipGetLastError());
+    return CZK_OK;
+}
+
+static int witness_map_post_common(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes, bool c_is_scratch) {
     if (!ctx || !ab || !c) return ctx ? set_err(ctx, CZK_ERR_ARG, "null witness_map argument") : CZK_ERR_ARG;
     CZK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t D = (size_t)1 << log_d;
     if (c_len > D) return set_err(ctx, CZK_ERR_SIZE, "witness_map: more evaluations than the domain holds");
     DomainTables* d = nullptr;
     CZK_TRY(get_domain(ctx, log_d, &d));
+    if (c_is_scratch && (ctx->witness_map_short & 1)) {
+        // transforms are linear and coset_ifft(coset_fft(x)) = x, so coset_ifft((ab - coset_fft(ifft(c))) k) = k (coset_ifft(ab) - ifft(c)) in the field, and both sides
+        // are stored canonical: c is transformed once, and the subtraction and k ride on the last store of the coset inverse transform
+        CZK_TRY(ntt_device(ctx, (u64*)c, log_d, lanes, CZK_IFFT, c_len));
+        return ntt_device(ctx, (u64*)ab, log_d, lanes, CZK_COSET_IFFT, D, nullptr, 0, (const u64*)c, &d->vanishing_inv);
+    }
     CZK_TRY(ifft_coset_fft_device(ctx, c, log_d, lanes, c_len));
     size_t n = lanes * D;
     hipLaunchKernelGGL(k_sub_scale, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, (const u64*)ab, (const u64*)c, d->vanishing_inv, (u64*)ab, n);
     CZK_HIP(ctx, hipGetLastError());
     CZK_TRY(ntt_device(ctx, ab, log_d, lanes, CZK_COSET_IFFT, D));
     return CZK_OK;
+}
+
+extern "C" int czk_witness_map_post(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes) {
+    return witness_map_post_common(ctx, ab, c, c_len, log_d, lanes, false);
+}
+
+// czk_witness_map_post for a caller that needs h alone: `c` is scratch, which lets the call transform it once instead of twice
+extern "C" int czk_witness_map_post_h(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes) {
+    return witness_map_post_common(ctx, ab, c, c_len, log_d, lanes, true);
 }

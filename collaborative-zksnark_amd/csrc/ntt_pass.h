@@ -25,7 +25,9 @@ struct Pass2Args {
     const u32* prescale;  // g^i 2^261 (first pass of a coset fft) or null
     const u32* posttab;   // size_inv g^-i 2^261 (last pass of a coset ifft) or null
     FrU postconst;        // size_inv 2^261 (last pass of an ifft)
-    int post_mode;        // 0 none, 1 constant, 2 table
+    int post_mode;        // 0 none, 1 constant, 2 table, 3 table then (v - addend[k]) * postconst2, 4 canonical v + addend[k]
+    const u64* addend;    // post_mode 3 / 4: canonical lanes read at the OUTPUT index (lane stride = lane_stride), never the lanes being written
+    FrU postconst2;       // post_mode 3: the constant that follows the subtraction, 2^261 form
     unsigned n;           // log2 D
     unsigned s_lo;        // lowest stage bit of this pass
     size_t in_len;        // elements >= in_len read as zero (only honoured when `first`)

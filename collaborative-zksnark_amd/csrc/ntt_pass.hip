@@ -153,7 +153,15 @@ __device__ __forceinline__ FrU load_input(const Pass2Args& a, const u64* in, siz
     if (a.prescale) v = fru_mul(v, tab_load(a.prescale, gi));   // distribute_powers(g) on the un-resized input (domain/mod.rs:93-106, 139-142)
     return v;
 }
-__device__ __forceinline__ void store_output(const Pass2Args& a, u64* out, size_t k, const FrU& v, bool last) {
+// post_mode 3 (R1CStoQAP::witness_map's h = Z(g)^-1 (coset_ifft(ab) - ifft(c)), r1cs_to_qap.rs:102-110 with the transform of c cancelled): bounds in units of r --
+//   t = v * posttab[k] is a multiply output: normalised limbs, < 2 r (v < 384.2 < 440, the table is canonical); the addend is canonical: limbs < 2^29, < r,
+//   top limb <= r >> 232 <= (2 r >> 232) - 1, which is what FruC<2, 1> asks of a subtrahend; d = t - c + 2 r < 4 r with limbs < 2^29 + 0.8 * 2^30 < 2^31.4;
+//   d * postconst2 (canonical) < r (1 + 4 / 440) + ... < 2 r: a multiply output again, so fru_canon_mulout brings it to [0, r) as for modes 1 and 2.
+// post_mode 4 (a forward transform plus a canonical vector): the canonical output and the canonical addend meet in the saturated form (one fp_add).
+// PM: 0 = the modes 0 .. 2 by a.post_mode, as every pass but a transform's last and the last passes without an addend run; 3 / 4 = a kernel of its own each
+// (k_ntt2_final<C, PM>), so that the kernels of modes 0 .. 2 are the ones they were.
+template <int PM = 0>
+__device__ __forceinline__ void store_output(const Pass2Args& a, u64* out, size_t k, const FrU& v, bool last, const u64* addend = nullptr) {
     if (!last && NTT2_SCRATCH_2R && !NTT2_LAZY_SCRATCH) {   // scratch format 2: < 2 r, packed; no conditional subtraction
         fp_store<FrParams>(out + 4 * k, fru_pack(fru_reduce_2r(v)));
         return;
@@ -166,7 +174,11 @@ __device__ __forceinline__ void store_output(const Pass2Args& a, u64* out, size_
         return;
     }
     Fr s;
-    if (last && a.post_mode == 1) s = fru_canon_mulout(fru_mul(v, a.postconst));               // * size_inv (fft.rs:26-29)
+    if constexpr (PM == 3) {
+        const FrU d = fru_sub<2, 1>(fru_mul(v, tab_load(a.posttab, k)), fru_unpack(fp_load<FrParams>(addend + 4 * k)));
+        s = fru_canon_mulout(fru_mul(d, a.postconst2));
+    } else if constexpr (PM == 4) s = fp_add(fru_canon(v), fp_load<FrParams>(addend + 4 * k));
+    else if (last && a.post_mode == 1) s = fru_canon_mulout(fru_mul(v, a.postconst));               // * size_inv (fft.rs:26-29)
     else if (last && a.post_mode == 2) s = fru_canon_mulout(fru_mul(v, tab_load(a.posttab, k)));   // * size_inv g^-i (domain/mod.rs:99-106)
     else s = fru_canon(v);
     fp_store<FrParams>(out + 4 * k, s);
@@ -272,8 +284,8 @@ __global__ __launch_bounds__((1 << K) * 2) void k_ntt2_strided(Pass2Args a) {
 // the transposed store is the bit-reversal permutation (derange, fft.rs:253-260) and still writes 512-byte runs.
 // LDS: chunk t at row stride RS = 2^C + 1 words per limb plane.
 // ------------------------------------------------------------------------------------------------------------
-template <int C, int B0, int RB, int KB, bool FROM_GLOBAL, bool TO_GLOBAL>
-__device__ __forceinline__ void final_step(const Pass2Args& a, u32* smem, const u64* in, u64* out, unsigned blk) {
+template <int C, int B0, int RB, int KB, bool FROM_GLOBAL, bool TO_GLOBAL, int PM = 0>
+__device__ __forceinline__ void final_step(const Pass2Args& a, u32* smem, const u64* in, u64* out, unsigned blk, const u64* addend = nullptr) {
     constexpr int LEN = 1 << C, RS = LEN + 1, NEL = RS * NTT2_T, R = 1 << RB, GROUPS = 8 / R, NTHR = LEN * NTT2_T / 8;
     constexpr int OB = C - RB;   // bits of l outside the step
     const unsigned hb = a.n - C;
@@ -330,7 +342,7 @@ __device__ __forceinline__ void final_step(const Pass2Args& a, u32* smem, const 
             const unsigned l = l0 | ((unsigned)k << B0);
             if constexpr (TO_GLOBAL) {
                 const size_t ko = ((size_t)(__brev(l) >> (32 - C)) << hb) | chunk;
-                store_output(a, out, ko, x[k], true);
+                store_output<PM>(a, out, ko, x[k], true, addend);
             } else {
                 lds_put9<NEL>(smem, t * RS + l, x[k]);
             }
@@ -338,26 +350,27 @@ __device__ __forceinline__ void final_step(const Pass2Args& a, u32* smem, const 
     }
 }
 
-template <int C>
+template <int C, int PM>
 __global__ __launch_bounds__((1 << C) * 2) void k_ntt2_final(Pass2Args a) {   // input: scratch lanes
     extern __shared__ __attribute__((aligned(16))) u32 smem2[];
     constexpr int W = NTT2_SCRATCH_2R ? 2 : 1;   // inputs < 2 r
     const u64* in = (const u64*)((const char*)a.in + NTT2_SCRATCH_ELEM_BYTES * a.lane_stride * blockIdx.y);
     u64* out = a.out + 4 * a.lane_stride * blockIdx.y;
+    const u64* addend = PM ? a.addend + 4 * a.lane_stride * blockIdx.y : nullptr;
     if constexpr (C == 7) {
         final_step<7, 4, 3, 2 * W, true, false>(a, smem2, in, out, blockIdx.x);
         __syncthreads();
         final_step<7, 2, 2, 16 * W, false, false>(a, smem2, in, out, blockIdx.x);
         __syncthreads();
-        final_step<7, 0, 2, 64 * W, false, true>(a, smem2, in, out, blockIdx.x);
+        final_step<7, 0, 2, 64 * W, false, true, PM>(a, smem2, in, out, blockIdx.x, addend);
     } else if constexpr (C == 6) {
         final_step<6, 3, 3, 2 * W, true, false>(a, smem2, in, out, blockIdx.x);
         __syncthreads();
-        final_step<6, 0, 3, 16 * W, false, true>(a, smem2, in, out, blockIdx.x);
+        final_step<6, 0, 3, 16 * W, false, true, PM>(a, smem2, in, out, blockIdx.x, addend);
     } else {
         final_step<5, 2, 3, 2 * W, true, false>(a, smem2, in, out, blockIdx.x);
         __syncthreads();
-        final_step<5, 0, 2, 16 * W, false, true>(a, smem2, in, out, blockIdx.x);
+        final_step<5, 0, 2, 16 * W, false, true, PM>(a, smem2, in, out, blockIdx.x, addend);
     }
 }
 
@@ -530,9 +543,16 @@ int launch_ntt2_pass(czk_ctx* ctx, const Pass2Args& a, unsigned K, bool last, si
         }
     } else {
         const size_t lds = (size_t)9 * (((size_t)1 << K) + 1) * NTT2_T * 4;
-        if (K == 7) hipLaunchKernelGGL(k_ntt2_final<7>, grid, block, lds, ctx->stream, a);
-        else if (K == 6) hipLaunchKernelGGL(k_ntt2_final<6>, grid, block, lds, ctx->stream, a);
-        else hipLaunchKernelGGL(k_ntt2_final<5>, grid, block, lds, ctx->stream, a);
+#define CZK_FINAL(PM)                                                                                  \
+    do {                                                                                               \
+        if (K == 7) hipLaunchKernelGGL((k_ntt2_final<7, PM>), grid, block, lds, ctx->stream, a);      \
+        else if (K == 6) hipLaunchKernelGGL((k_ntt2_final<6, PM>), grid, block, lds, ctx->stream, a); \
+        else hipLaunchKernelGGL((k_ntt2_final<5, PM>), grid, block, lds, ctx->stream, a);             \
+    } while (0)
+        if (a.post_mode == 3) CZK_FINAL(3);
+        else if (a.post_mode == 4) CZK_FINAL(4);
+        else CZK_FINAL(0);
+#undef CZK_FINAL
     }
     CZK_HIP(ctx, hipGetLastError());
     return CZK_OK;

@@ -322,6 +322,24 @@ class Groth16Local:
         for p in range(1, self.P):
             ctx.fr_vec_op(SUB, chk.data_ptr(), shares[2 * p + 1].data_ptr(), out=chk.data_ptr(), n=D, mem=M)
 
+    def _beaver_product(self):
+        """a, b -> ab = batch_product_in_place -> S::batch_mul (share/field.rs:97-127): the transforms of witness_map_pre with (s + x), (o + y) added on
+        their last store, two opens, combine -- the opens and every lane's combine as one kernel where every party's SPDZ lanes are on this GPU"""
+        czk, ctx = self.czk, self.ctx
+        D, N, L, ld = self.D, self.N, self.lanes, self.log_d
+        M = czk.CZK_MEM_DEVICE
+        ctx.witness_map_pre_masked(self.a.data_ptr(), self.b.data_ptr(), self.tx.data_ptr(), self.ty.data_ptr(), ld, L, a_len=N + 2, b_len=N)
+        if self.scheme == "spdz" and len(self.local) == self.P and L == 2 * self.P:
+            ctx.spdz_open_combine(self.a.data_ptr(), self.b.data_ptr(), self.tx.data_ptr(), self.ty.data_ptr(), self.tz.data_ptr(), self.P,
+                                  sum(1 << ln for ln in self.king_lanes), self.sx.data_ptr(), self.oy.data_ptr(), self.chk[0].data_ptr(),
+                                  self.chk[1].data_ptr(), self.ab.data_ptr(), D)
+            return
+        self._open(self.a, self.sx, self.chk[0])
+        self._open(self.b, self.oy, self.chk[1])
+        for ln in range(L):
+            ctx.fr_beaver_combine(self.tx[ln].data_ptr(), self.ty[ln].data_ptr(), self.tz[ln].data_ptr(), self.sx.data_ptr(),
+                                  self.oy.data_ptr(), ln in self.king_lanes, out=self.ab[ln].data_ptr(), n=D, mem=M)
+
     def _gsz_batch_mult(self):
         """gsz20::batch_mult (share/gsz20/mod.rs:556-595) on the lanes of a, b -> ab: x.val *= y.val; x.degree *= 2; x.val += r2.val; the king opens
         the degree-2t shares and hands the value to every party (batch_king_compute, f = identity: :494-527); shift_res.val -= r.val."""
@@ -383,19 +401,12 @@ class Groth16Local:
         ctx.r1cs_matvec(self.mat_a, self.full.data_ptr(), lanes=L, out=self.a.data_ptr(), z_stride=N + 2, out_stride=D, mem=M)
         ctx.r1cs_matvec(self.mat_b, self.full.data_ptr(), lanes=L, out=self.b.data_ptr(), z_stride=N + 2, out_stride=D, mem=M)
         ctx.r1cs_matvec(self.mat_c, self.full.data_ptr(), lanes=L, out=self.c.data_ptr(), z_stride=N + 2, out_stride=D, mem=M)
-        ctx.witness_map_pre(self.a.data_ptr(), self.b.data_ptr(), ld, L, a_len=N + 2, b_len=N)   # ifft, ifft, coset_fft, coset_fft
         if self.scheme == "gsz":
+            ctx.witness_map_pre(self.a.data_ptr(), self.b.data_ptr(), ld, L, a_len=N + 2, b_len=N)   # ifft, ifft, coset_fft, coset_fft
             self._gsz_batch_mult()
         else:
-            # batch_product_in_place -> S::batch_mul (share/field.rs:97-127): (s + x), (o + y), two opens, combine
-            ctx.fr_vec_op(ADD, self.a.data_ptr(), self.tx.data_ptr(), out=self.a.data_ptr(), n=L * D, mem=M)
-            ctx.fr_vec_op(ADD, self.b.data_ptr(), self.ty.data_ptr(), out=self.b.data_ptr(), n=L * D, mem=M)
-            self._open(self.a, self.sx, self.chk[0])
-            self._open(self.b, self.oy, self.chk[1])
-            for ln in range(L):
-                ctx.fr_beaver_combine(self.tx[ln].data_ptr(), self.ty[ln].data_ptr(), self.tz[ln].data_ptr(), self.sx.data_ptr(),
-                                      self.oy.data_ptr(), ln in self.king_lanes, out=self.ab[ln].data_ptr(), n=D, mem=M)
-        ctx.witness_map_post(self.ab.data_ptr(), self.c.data_ptr(), ld, L, c_len=N)     # h = ab
+            self._beaver_product()
+        ctx.witness_map_post_h(self.ab.data_ptr(), self.c.data_ptr(), ld, L, c_len=N)   # h = ab (c is rebuilt by the next step's mat-vec)
         # --- the h MSM (prover.rs:104) needs the witness map's output; NOT flagged stable: the next proof's witness
         # map overwrites `ab`, so the context's stream waits for this MSM's digit extraction (library-side ordering)
         if self.base_split is None:
@@ -418,15 +429,8 @@ class Groth16Local:
         ctx.r1cs_matvec(self.mat_a, self.full.data_ptr(), lanes=L, out=self.a.data_ptr(), z_stride=N + 2, out_stride=D, mem=M)
         ctx.r1cs_matvec(self.mat_b, self.full.data_ptr(), lanes=L, out=self.b.data_ptr(), z_stride=N + 2, out_stride=D, mem=M)
         ctx.r1cs_matvec(self.mat_c, self.full.data_ptr(), lanes=L, out=self.c.data_ptr(), z_stride=N + 2, out_stride=D, mem=M)
-        ctx.witness_map_pre(self.a.data_ptr(), self.b.data_ptr(), ld, L, a_len=N + 2, b_len=N)
-        ctx.fr_vec_op(ADD, self.a.data_ptr(), self.tx.data_ptr(), out=self.a.data_ptr(), n=L * D, mem=M)
-        ctx.fr_vec_op(ADD, self.b.data_ptr(), self.ty.data_ptr(), out=self.b.data_ptr(), n=L * D, mem=M)
-        self._open(self.a, self.sx, self.chk[0])
-        self._open(self.b, self.oy, self.chk[1])
-        for ln in range(L):
-            ctx.fr_beaver_combine(self.tx[ln].data_ptr(), self.ty[ln].data_ptr(), self.tz[ln].data_ptr(), self.sx.data_ptr(),
-                                  self.oy.data_ptr(), ln in self.king_lanes, out=self.ab[ln].data_ptr(), n=D, mem=M)
-        ctx.witness_map_post(self.ab.data_ptr(), self.c.data_ptr(), ld, L, c_len=N)
+        self._beaver_product()
+        ctx.witness_map_post_h(self.ab.data_ptr(), self.c.data_ptr(), ld, L, c_len=N)
         self.ab_sh.copy_(self.ab[0::2])                      # the sh lanes of h, contiguous (torch's stream == the context's stream)
         ctx.msm_async(self.h_query, self.ab_sh.data_ptr(), D, P, MONT, r["h"])
         if sync:

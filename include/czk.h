@@ -135,6 +135,9 @@ const char* czk_version(void);
  *   "ntt_gen1" 0/1              first-generation NTT passes (the small-domain kernels) for every size
  *   "ntt_fuse_pairs" 0/1        czk_witness_map_pre/post: the last pass of an inverse transform and the first pass of the coset transform that follows it
  *                               as one kernel where their tiles line up (2^21, 2^18, 2^15, 2^14, 2^12); same values; default 0 (+ 0.5 % per proof measured)
+ *   "witness_map_short" 0..7    a bit set (default 7): 1 = czk_witness_map_post_h transforms c once (6 transforms per witness map instead of 7), 2 = czk_witness_map_pre_masked
+ *                               adds its masks on the transforms' last store, 4 = czk_spdz_open_combine is one kernel; a clear bit = the same values from the longer
+ *                               kernel sequence (without bit 1, `c` holds coset_fft(ifft(c)) instead of ifft(c) after czk_witness_map_post_h: scratch either way)
  *   "net_create_timeout_ms" 0..3600000   how long czk_net_create on this context waits for its peers at the rendezvous (0 = the default, 120 s;
  *                               afterwards the communicator's own "timeout_ms" option applies)
  * Any other name is CZK_ERR_ARG.  The call drains the context's enqueued work first, so an option never changes under a running proof.
@@ -238,6 +241,15 @@ int czk_fr_beaver_combine(czk_ctx* ctx, const uint64_t* x, const uint64_t* y, co
  *   check[i]  = sum_p (mac_share_p * value[i] - mac_p[i]),  mac_share_p = (p == 0)   (spdz.rs:31-37, :176-183)
  * *out_bad (host) receives the number of i with check[i] != 0 (the reference asserts it is 0). */
 int czk_fr_spdz_open(czk_ctx* ctx, const uint64_t* shares, size_t parties, size_t n, uint64_t* out_value, uint64_t* out_bad);
+/* Both opens of S::batch_mul and its local combine (share/field.rs:97-127, share/spdz.rs:166-185) in one kernel, for `parties` (1..32) parties whose lanes are all on
+ * this GPU.  DEVICE memory, every vector n Fr per lane, lanes party-major (lane 2 p = sh, 2 p + 1 = mac of party p) and n elements apart:
+ *   a, b        2 parties lanes each: the masked factors s + x and o + y        tx, ty, tz   2 parties lanes each: the triple's shares
+ *   sx[i] = sum_p a_sh_p[i], oy[i] = sum_p b_sh_p[i]                                      (n Fr each)
+ *   chk_a[i] = sx[i] - sum_p a_mac_p[i], chk_b[i] = oy[i] - sum_p b_mac_p[i]             (n Fr each; all zero unless a MAC is broken)
+ *   ab_ln[i] = tz_ln[i] - ty_ln[i] sx[i] - tx_ln[i] oy[i] + (bit ln of king_mask ? sx[i] oy[i] : 0)      (2 parties lanes)
+ * The outputs must not overlap the inputs or one another.  Same values as czk_fr_vec_op per open and czk_fr_beaver_combine per lane. */
+int czk_spdz_open_combine(czk_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, size_t parties,
+                          uint64_t king_mask, uint64_t* sx, uint64_t* oy, uint64_t* chk_a, uint64_t* chk_b, uint64_t* ab, size_t n);
 
 /* The same open round by round, as the reference runs it when every party is its own process (share/spdz.rs:166-185) --
  * between the calls the caller moves the vectors with mpc-net's broadcast / atomic_broadcast (RCCL all-gather here):
@@ -560,11 +572,18 @@ int czk_fr_lagrange_coefficients(czk_ctx* ctx, unsigned log_d, const uint64_t* t
  *   czk_witness_map_pre : a <- coset_fft(ifft(a)), b <- coset_fft(ifft(b))                       (:85-89)
  *   [caller: ab = batch_product(a, b) -- Beaver opens for shares, czk_fr_vec_op(MUL) for a single prover] (:92)
  *   czk_witness_map_post: c <- coset_fft(ifft(c)); ab <- coset_ifft((ab - c) * Z(g)^-1)          (:102-110)
+ *   czk_witness_map_post_h: the same ab for a caller that needs h alone: c <- ifft(c); ab <- (coset_ifft(ab) - c) * Z(g)^-1 -- the same field elements
+ *     (transforms are linear and coset_ifft undoes coset_fft), with c transformed once instead of twice; `c` is scratch afterwards
+ *   czk_witness_map_pre_masked: a <- coset_fft(ifft(a)) + mask_a, b <- coset_fft(ifft(b)) + mask_b -- what a Beaver product needs of a and b
+ *     (share/field.rs:103-104); masks: lanes x D canonical Fr, not overlapping a or b
  * h = ab on return.  a_len / b_len / c_len <= D: evaluations present in each lane (num_constraints + num_inputs for a,
  * num_constraints for b and c); elements beyond them are the reference's `vec![zero; domain_size]` padding (:66-67, :94)
  * and are never read -- the first NTT pass zero-extends. */
 int czk_witness_map_pre(czk_ctx* ctx, uint64_t* a, size_t a_len, uint64_t* b, size_t b_len, unsigned log_d, size_t lanes);
+int czk_witness_map_pre_masked(czk_ctx* ctx, uint64_t* a, size_t a_len, uint64_t* b, size_t b_len, const uint64_t* mask_a, const uint64_t* mask_b, unsigned log_d,
+                               size_t lanes);
 int czk_witness_map_post(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes);
+int czk_witness_map_post_h(czk_ctx* ctx, uint64_t* ab, uint64_t* c, size_t c_len, unsigned log_d, size_t lanes);
 
 /* ---- square roots and the reference's byte format of curve points -------------------------------- */
 /* SquareRootField::sqrt over Fq (ext = 1: n x 6 u64) or Fq2 (ext = 2: n x 12 u64), Montgomery form, one thread per element.

@@ -747,6 +747,25 @@ struct R1CStoQAP {
         ctx.check(czk_witness_map_post(ctx.raw(), ab.data(), c.data(), c.len, domain.log_size_of_group, lanes));
         ab.len = c.len = domain.size();
     }
+
+    // ... for a Beaver product, which needs a and b only as a + x and b + y (share/field.rs:103-104): the triple's x, y lanes go in as masks and
+    // `batch_product` receives the masked lanes (czk_witness_map_pre_masked adds them on the transforms' last store); `c` is scratch on return
+    // (czk_witness_map_post_h)
+    template <class BatchProduct>
+    static void witness_map(const Radix2EvaluationDomain& domain, DeviceLanes& a, DeviceLanes& b, DeviceLanes& c, DeviceLanes& ab, const DeviceLanes& mask_a,
+                            const DeviceLanes& mask_b, BatchProduct&& batch_product) {
+        const Context& ctx = domain.ctx();
+        const size_t lanes = a.lanes();
+        if (a.capacity() != domain.size() || b.capacity() != domain.size() || c.capacity() != domain.size() || ab.capacity() != domain.size() ||
+            mask_a.capacity() != domain.size() || mask_b.capacity() != domain.size() || b.lanes() != lanes || c.lanes() != lanes || ab.lanes() != lanes ||
+            mask_a.lanes() != lanes || mask_b.lanes() != lanes)
+            throw Panic(CZK_ERR_SIZE, "witness_map: lanes must have the domain's size");
+        ctx.check(czk_witness_map_pre_masked(ctx.raw(), a.data(), a.len, b.data(), b.len, mask_a.data(), mask_b.data(), domain.log_size_of_group, lanes));
+        a.len = b.len = domain.size();
+        batch_product(a, b, ab);
+        ctx.check(czk_witness_map_post_h(ctx.raw(), ab.data(), c.data(), c.len, domain.log_size_of_group, lanes));
+        ab.len = c.len = domain.size();
+    }
 };
 
 // ---- pairing and Groth16 verification (czk_pairing*, czk_groth16_*) ------------------------------------------------------------

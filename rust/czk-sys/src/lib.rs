@@ -110,6 +110,7 @@ extern "C" {
     pub fn czk_fr_powers(ctx: *mut czk_ctx, g: *const u64, c: *const u64, n: usize, out: *mut u64, mem: c_int) -> c_int;
     pub fn czk_fr_beaver_combine(ctx: *mut czk_ctx, x: *const u64, y: *const u64, z: *const u64, sx: *const u64, oy: *const u64, add_open: c_int, out: *mut u64, n: usize, mem: c_int) -> c_int;
     pub fn czk_fr_spdz_open(ctx: *mut czk_ctx, shares: *const u64, parties: usize, n: usize, out_value: *mut u64, out_bad: *mut u64) -> c_int;
+    pub fn czk_spdz_open_combine(ctx: *mut czk_ctx, a: *const u64, b: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, parties: usize, king_mask: u64, sx: *mut u64, oy: *mut u64, chk_a: *mut u64, chk_b: *mut u64, ab: *mut u64, n: usize) -> c_int;
     pub fn czk_fr_lanes_sum(ctx: *mut czk_ctx, x: *const u64, k: usize, n: usize, out: *mut u64, out_nonzero: *mut u64) -> c_int;
     pub fn czk_fr_spdz_dx(ctx: *mut czk_ctx, value: *const u64, mac: *const u64, mac_share: *const u64, out: *mut u64, n: usize) -> c_int;
     pub fn czk_share_domain_constants(ctx: *mut czk_ctx, parties: usize, out12: *mut u64) -> c_int;
@@ -176,7 +177,9 @@ extern "C" {
     pub fn czk_fixed_base_msm(ctx: *mut czk_ctx, fb: *const czk_fixed_base, scalars: *const u64, n: usize, scalar_form: c_int, out_aff: *mut u64, out_inf: *mut u8, mem: c_int) -> c_int;
     pub fn czk_fr_lagrange_coefficients(ctx: *mut czk_ctx, log_d: c_uint, tau: *const u64, out: *mut u64, n_out: usize, mem: c_int) -> c_int;
     pub fn czk_witness_map_pre(ctx: *mut czk_ctx, a: *mut u64, a_len: usize, b: *mut u64, b_len: usize, log_d: c_uint, lanes: usize) -> c_int;
+    pub fn czk_witness_map_pre_masked(ctx: *mut czk_ctx, a: *mut u64, a_len: usize, b: *mut u64, b_len: usize, mask_a: *const u64, mask_b: *const u64, log_d: c_uint, lanes: usize) -> c_int;
     pub fn czk_witness_map_post(ctx: *mut czk_ctx, ab: *mut u64, c: *mut u64, c_len: usize, log_d: c_uint, lanes: usize) -> c_int;
+    pub fn czk_witness_map_post_h(ctx: *mut czk_ctx, ab: *mut u64, c: *mut u64, c_len: usize, log_d: c_uint, lanes: usize) -> c_int;
     pub fn czk_fq_sqrt(ctx: *mut czk_ctx, ext: c_int, a: *const u64, n: usize, out: *mut u64, out_exists: *mut u8, mem: c_int) -> c_int;
     pub fn czk_points_serialize(ctx: *mut czk_ctx, group: c_int, pts: *const u64, inf: *const u8, n: usize, compressed: c_int, out_bytes: *mut u8, mem: c_int) -> c_int;
     pub fn czk_points_deserialize(ctx: *mut czk_ctx, group: c_int, bytes: *const u8, n: usize, flags: c_int, out_pts: *mut u64, out_inf: *mut u8, out_status: *mut u8, out_bad: *mut usize, out_first_bad: *mut usize, mem: c_int) -> c_int;

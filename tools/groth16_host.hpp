@@ -285,7 +285,7 @@ class Groth16Host {
         mat_a_->evaluate(*full_, *a_);
         mat_b_->evaluate(*full_, *b_);
         mat_c_->evaluate(*full_, *c_);
-        czk::R1CStoQAP::witness_map(*domain_, *a_, *b_, *c_, *ab_,
+        czk::R1CStoQAP::witness_map(*domain_, *a_, *b_, *c_, *ab_, *tx_, *ty_,
                                     [this](czk::DeviceLanes& x, czk::DeviceLanes& y, czk::DeviceLanes& xy) { batch_product(x, y, xy); });
         // the h MSM (prover.rs:104) consumes the witness map's output; not stable: the next proof overwrites `ab`
         czk::multi_scalar_mul_async(*h_query_, *ab_, D, r.h.data(), false);
@@ -372,11 +372,16 @@ class Groth16Host {
         for (size_t p = 1; p < P; p++) ctx.check(czk_fr_vec_op(ctx.raw(), CZK_OP_SUB, chk, shares.data(2 * p + 1), chk, D, M));
     }
 
-    // F::batch_product_in_place -> S::batch_mul (share/field.rs:97-127): (s + x), (o + y), two opens, local combine
+    // F::batch_product_in_place -> S::batch_mul (share/field.rs:97-127) on a = s + x, b = o + y (the witness map added the masks): two opens, local combine
     void batch_product(czk::DeviceLanes& a, czk::DeviceLanes& b, czk::DeviceLanes& ab) {
         const int M = CZK_MEM_DEVICE;
-        ctx.check(czk_fr_vec_op(ctx.raw(), CZK_OP_ADD, a.data(), tx_->data(), a.data(), L * D, M));
-        ctx.check(czk_fr_vec_op(ctx.raw(), CZK_OP_ADD, b.data(), ty_->data(), b.data(), L * D, M));
+        if (local_.size() == P && L <= 64) {   // every party's lanes are here: both opens and the combine of every lane in one kernel
+            uint64_t king = 0;
+            for (size_t ln = 0; ln < L; ln++) king |= (uint64_t)(king_lane(ln) ? 1 : 0) << ln;
+            ctx.check(czk_spdz_open_combine(ctx.raw(), a.data(), b.data(), tx_->data(), ty_->data(), tz_->data(), P, king, sx_->data(), oy_->data(), chk_->data(0),
+                                            chk_->data(1), ab.data(), D));
+            return;
+        }
         open(a, *sx_, chk_->data(0));
         open(b, *oy_, chk_->data(1));
         for (size_t ln = 0; ln < L; ln++)
