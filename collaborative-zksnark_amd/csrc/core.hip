@@ -431,6 +431,7 @@ const OptDesc OPTIONS[] = {
     {"msm_fixed_c", 0, 1, false, [](czk_ctx* c, long v) { c->msm_fixed_c = v != 0; }},
     {"msm_window_g1", 0, 22, false, [](czk_ctx* c, long v) { c->msm_c_g1 = (unsigned)v; }},
     {"msm_window_g2", 0, 22, false, [](czk_ctx* c, long v) { c->msm_c_g2 = (unsigned)v; }},
+    {"msm_reduce_lean", 0, 3, false, [](czk_ctx* c, long v) { c->msm_reduce_lean = (uint8_t)v; }},
     {"ntt_gen1", 0, 1, false, [](czk_ctx* c, long v) { c->ntt_gen1 = v != 0; }},
     {"ntt_fuse_pairs", 0, 1, false, [](czk_ctx* c, long v) { c->ntt_fuse_pairs = v != 0; }},
     {"witness_map_short", 0, 7, false, [](czk_ctx* c, long v) { c->witness_map_short = (uint8_t)v; }},

@@ -173,6 +173,8 @@ struct czk_ctx {
                                      // measured + 0.5 % per Groth16 proof (EXPERIMENTS.md section 14), below the 1 % adoption bar: off by default
     uint8_t witness_map_short = 7;   // "witness_map_short", a bit set: 1 = czk_witness_map_post_h transforms c once, 2 = czk_witness_map_pre_masked adds on the transforms' last store,
                                      // 4 = czk_spdz_open_combine is one kernel; a clear bit = the same values from the kernel sequence of before (EXPERIMENTS.md section 22)
+    uint8_t msm_reduce_lean = 3;     // "msm_reduce_lean", a bit set for the twisted Edwards bucket reduction: 1 = no additions to the neutral element, 2 = one 2 D T product for both
+                                     // additions of a running sum (with bit 1); a clear bit = the kernel of before (msm_acc.h k_reduce_level_p LEAN, EXPERIMENTS.md section 23)
     bool ntt_gen1 = false;           // "ntt_gen1": first-generation NTT passes (ntt.hip, the small-domain kernels) for every size
     bool profiling = false;
     std::map<std::string, czk::ProfEntry> prof;
@@ -427,10 +429,10 @@ void launch_heavy_g1(hipStream_t st, const u64* pts, const u32* sorted, const u3
                      u64* buckets, unsigned lanes, const uint8_t* dirty, u32* hdr, u32* items, u32* heavy, u64* partials, u32 cap, int unsat, int ubuckets);
 // the bucket reduction on u-form buckets (G1: buckets stay in the unsaturated residue system of fqu.h until the last step)
 void launch_reduce_level_g1_u(hipStream_t st, const u64* P, const u64* E, size_t n_in, unsigned L, unsigned scale_dbl, u64* Po, u64* Eo, size_t n_out,
-                              unsigned lanes, int te);
+                              unsigned lanes, int te, int lean);
 void launch_finish_g1_u(hipStream_t st, const u64* P, const u64* E, size_t segs, u64* out, int te);
 void launch_reduce_tail_g1_u(hipStream_t st, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl, u64* scratch, u64* sums, u64* out, unsigned lanes,
-                             int te);
+                             int te, int lean);
 // G1 in twisted Edwards form (te.h): table conversion at registration, bucket accumulation, over-full buckets
 void launch_sw_to_te_niels(hipStream_t st, const u64* aff, const uint8_t* inf, size_t n, u64* scratch, u64* out, u32* bad);
 void launch_accumulate_g1_te(czk_ctx* ctx, hipStream_t st, const u64* pts, const u32* sorted, const u32* offsets, const u32* counts, const u32* perm, size_t B,

@@ -54,6 +54,7 @@ struct MsmPlan : MsmSortDims {
     const czk_bases* b;
     size_t lvl0, need_sort, need_red, need_aff, aff_scratch, out_bytes;   // lvl0: entries of the first reduction level
     u32 heavy_cap;                   // >= number of 256-entry work items of over-full buckets (msm_acc.h HEAVY_SUB)
+    int lean;                        // "msm_reduce_lean" as this call found it (twisted Edwards reduction kernels, msm_acc.h)
     int JW, XW, ub;                  // ub: buckets stay in u-form through the reduction (b->te: twisted Edwards tables and buckets, te.h; b->unsat: u-form tables)
     bool g1, stable, same, key_valid, may_reuse, any_inf, drop_wait;
     AffArgs aff;                     // lab, batched-affine rounds (rounds != 0): the sizes
@@ -106,6 +107,7 @@ static int msm_plan(czk_ctx* ctx, const czk_bases* b, const u64* scalars, size_t
     p.heavy_cap = (u32)(p.lanes * p.total / 256 + 64);
     p.need_red = p.lanes * (p.B * p.XW * 8 + 4 * p.lvl0 * p.XW * 8 + p.JW * 8 + p.B + (size_t)12 * 513 * p.XW * 8) + (size_t)p.heavy_cap * (p.XW * 8 + 32) + (1 << 17);
     p.out_bytes = p.lanes * p.JW * 8;
+    p.lean = ctx->msm_reduce_lean;
     p.ub = 1;   // product build: every key's tables are in the unsaturated residue system, buckets stay in u-form through the reduction
 #ifdef CZK_LAB
     // G1 buckets stay in u-form through the reduction (k_reduce_*_u) unless the batched-affine rounds (which finish on saturated level points) or
@@ -263,7 +265,7 @@ static int msm_stage_accumulate(czk_ctx* ctx, MsmSlot& slot, const MsmPlan& p, c
 
 static void launch_reduce_level(hipStream_t sr, const MsmPlan& p, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl, u64* Po, u64* Eo, size_t n_out) {
     if (!p.g1) launch_reduce_level_g2(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, (unsigned)p.lanes, p.ub);
-    else if (p.ub) launch_reduce_level_g1_u(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, (unsigned)p.lanes, p.b->te);
+    else if (p.ub) launch_reduce_level_g1_u(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, (unsigned)p.lanes, p.b->te, p.lean);
 #ifdef CZK_LAB
     else launch_reduce_level_g1(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, (unsigned)p.lanes);
 #endif
@@ -272,7 +274,7 @@ static void launch_reduce_level(hipStream_t sr, const MsmPlan& p, const u64* P, 
 static void launch_reduce_end(hipStream_t sr, const MsmPlan& p, const MsmBufs& w, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl) {
     const unsigned lanes = (unsigned)p.lanes;
     if (!p.g1) n_in > 1 ? launch_reduce_tail_g2(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes, p.ub) : launch_finish_g2(sr, P, E, lanes, w.result, p.ub);
-    else if (p.ub) n_in > 1 ? launch_reduce_tail_g1_u(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes, p.b->te) : launch_finish_g1_u(sr, P, E, lanes, w.result, p.b->te);
+    else if (p.ub) n_in > 1 ? launch_reduce_tail_g1_u(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes, p.b->te, p.lean) : launch_finish_g1_u(sr, P, E, lanes, w.result, p.b->te);
 #ifdef CZK_LAB
     else n_in > 1 ? launch_reduce_tail_g1(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes) : launch_finish_g1(sr, P, E, lanes, w.result);
 #endif

@@ -264,8 +264,18 @@ __global__ void k_reduce_tail_finish(const u64* sums, unsigned scale_dbl, size_t
 // every intermediate array in u-form.  PT = the point type's operations: XyzzOps (fqu.h XYZZU, short Weierstrass G1), TeOps (te.h TEU,
 // twisted Edwards G1: unified additions, no infinity flag) or Xyzz2Ops (fq2pu.h XYZZU2, G2: one point per lane PAIR, PT::SHIFT = 1).
 // PT::JW = u64 words per point, PT::JACW = u64 words of the Jacobian result.
+//
+// LEAN (a bit set, option "msm_reduce_lean"; only for a PT without an infinity flag, PT::HAS_INF == false, i.e. TeOps -- xyzzu_add and
+// xyzzu2_add return at once when an operand is at infinity, a unified addition runs all of its multiplications whatever it is given):
+//   1  no additions to the neutral element: `running` starts as the chunk's last entry and A as the first running value (the level
+//      kernel), a thread's partial sum as its first entry (the tail kernel).  A chunk of one entry (a clipped last chunk) has
+//      nothing to put into A: it stays neutral.  Every bucket set the library makes is a power of two of at least 128 entries, so on
+//      its paths no chunk is clipped; the kernel is right for any n_in all the same.
+//   2  (with 1) PT::kt(running) = 2 D T of the running sum is computed once per entry and serves both additions the running sum takes
+//      part in, A += running and the next running += P: 17 multiplications per entry instead of 18 (te.h teu_add_kt).
+// LEAN = 0 is the kernel of before, entry for entry, and what the other point types are instantiated with.
 // ------------------------------------------------------------------------------------------------
-template <class PT>
+template <class PT, int LEAN = 0>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(PT::WAVES, PT::WAVES))) void k_reduce_level_p(const u64* P_in, const u64* E_in, size_t n_in, unsigned L,
                                                                                                     unsigned scale_dbl, u64* P_out, u64* E_out, size_t n_out) {
     constexpr int JW = PT::JW;
@@ -273,11 +283,34 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(PT::WAVES, 
     if (m >= n_out) return;
     const size_t seg = blockIdx.y;
     const u64* P = P_in + (size_t)JW * seg * n_in;
-    size_t start = m * L, end = start + L < n_in ? start + L : n_in;
+    size_t start = m * L, end = start + L < n_in ? start + L : n_in;   // start < n_in: m < n_out = ceil(n_in / L)
     typename PT::P running = PT::zero(), A = PT::zero();
-    for (size_t t = end; t-- > start;) {
-        PT::add(running, PT::load(P + JW * t));
-        if (t > start) PT::add(A, running);
+    if constexpr (LEAN == 0) {
+        for (size_t t = end; t-- > start;) {
+            PT::add(running, PT::load(P + JW * t));
+            if (t > start) PT::add(A, running);
+        }
+    } else {
+        static_assert(!PT::HAS_INF, "the lean running sums are for unified additions");
+        running = PT::load(P + JW * (end - 1));
+        if (end - start > 1) A = running;
+        if constexpr (LEAN & 2) {
+            typename PT::K kR = PT::kt(running);
+            for (size_t t = end - 1; t-- > start;) {
+                typename PT::P s = PT::load(P + JW * t);
+                PT::add_kt(s, running, kR);                // P[t] + running: addition commutes, and it is the running sum whose 2 D T is at hand
+                running = s;
+                if (t > start) {
+                    kR = PT::kt(running);
+                    PT::add_kt(A, running, kR);
+                }
+            }
+        } else {
+            for (size_t t = end - 1; t-- > start;) {
+                PT::add(running, PT::load(P + JW * t));
+                if (t > start) PT::add(A, running);
+            }
+        }
     }
     for (unsigned k = 0; k < scale_dbl; k++) PT::dbl(A);
     if (E_in) {
@@ -296,7 +329,7 @@ __global__ void k_finish_p(const u64* P, const u64* E, size_t segs, u64* out) {
     if (E) PT::add(r, PT::load(E + (size_t)JW * s));
     PT::store_jac(out + (size_t)PT::JACW * s, r);   // the result leaves as the reference's Jacobian triple, Montgomery form
 }
-template <class PT>
+template <class PT, int LEAN = 0>   // LEAN & 1: a thread's sum starts as its first entry (see k_reduce_level_p)
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(PT::WAVES, PT::WAVES))) void k_reduce_tail_sums_p(const u64* P_in, const u64* E_in, size_t n_in, u64* scratch,
                                                                                                         u64* sums) {
     constexpr int JW = PT::JW;
@@ -306,7 +339,23 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(PT::WAVES, 
     typename PT::P v = PT::zero();
     if (src) {
         src += (size_t)JW * seg * n_in;
-        for (size_t j = tid; j < n_in; j += NT)
+        size_t j = tid;
+        if constexpr (LEAN & 1) {
+            // the thread's first entry, j0 = tid + k NT: bit `which` of j0 is a bit of tid below log2(NT) -- then every entry of the thread
+            // qualifies, or none does -- and bit `which` - log2(NT) of k above
+            static_assert(!PT::HAS_INF, "the lean running sums are for unified additions");
+            constexpr unsigned LOG_NT = 7 - PT::SHIFT;
+            static_assert(NT == 1u << LOG_NT, "tail block size");
+            size_t j0 = tid;
+            if (which < 10) j0 = which < LOG_NT ? (((tid >> which) & 1) ? (size_t)tid : n_in) : tid + ((size_t)NT << (which - LOG_NT));
+            if (j0 < n_in) {
+                v = PT::load(src + JW * j0);
+                j = j0 + NT;
+            } else {
+                j = n_in;
+            }
+        }
+        for (; j < n_in; j += NT)
             if (which >= 10 || ((j >> which) & 1)) PT::add(v, PT::load(src + JW * j));
     }
     u64* sc = scratch + (size_t)JW * ((size_t)(seg * TAIL_BLOCKS + which) * TAIL_THREADS);
@@ -470,6 +519,7 @@ __global__ void k_convert_from_u(u64* pts, size_t n_coords) {
 // ---- the G1 point types of the u-form bucket reduction (k_reduce_*_p above) ----
 struct XyzzOps {
     static constexpr int WAVES = 2, JW = 24, JACW = 18, SHIFT = 0;
+    static constexpr bool HAS_INF = true;   // xyzzu_add returns at once when an operand is at infinity
     typedef XYZZU P;
     static __device__ __forceinline__ P zero() { return xyzzu_zero(); }
     static __device__ __forceinline__ P load(const u64* p) { return xyzzu_load(p); }
@@ -485,7 +535,11 @@ struct TeOps {
     // 3 waves per SIMD = at most 168 VGPRs: a reduction wave then fits NEXT to the two resident waves of k_accumulate_te (155 VGPRs
     // each) instead of taking one of their slots (same-box A/B: 80.6 against 81.2 ms per proof)
     static constexpr int WAVES = CZK_TERED_WAVES, JW = 24, JACW = 18, SHIFT = 0;
+    static constexpr bool HAS_INF = false;  // unified additions: the neutral element costs what any point costs (k_reduce_level_p LEAN)
     typedef TEU P;
+    typedef FqU K;
+    static __device__ __forceinline__ K kt(const P& a) { return teu_kt(a); }
+    static __device__ __forceinline__ void add_kt(P& a, const P& b, const K& kb) { teu_add_kt(a, b, kb); }
     static __device__ __forceinline__ P zero() { return teu_identity(); }
     static __device__ __forceinline__ P load(const u64* p) { return teu_load(p); }
     static __device__ __forceinline__ void store(u64* p, const P& a) { teu_store(p, a); }

@@ -116,12 +116,16 @@ void launch_reduce_tail_g1(hipStream_t st, const u64* P, const u64* E, size_t n_
     hipLaunchKernelGGL((k_reduce_tail_finish<Fq, 24, 0>), dim3((lanes + 63) / 64), dim3(64), 0, st, sums, scale_dbl, (size_t)lanes, out);
 }
 #endif   // CZK_LAB
-// the three steps of the bucket reduction on u-form buckets (msm_acc.h k_reduce_*_p); te = twisted Edwards buckets (te.h)
+// the three steps of the bucket reduction on u-form buckets (msm_acc.h k_reduce_*_p); te = twisted Edwards buckets (te.h), and for those
+// lean = the bits of "msm_reduce_lean" (msm_acc.h k_reduce_level_p LEAN: each value its own instantiation, 0 = the kernels of before; bit 2
+// alone changes nothing, the shared product belongs to the lean loop)
 void launch_reduce_level_g1_u(hipStream_t st, const u64* P, const u64* E, size_t n_in, unsigned L, unsigned scale_dbl, u64* Po, u64* Eo, size_t n_out,
-                              unsigned lanes, int te) {
+                              unsigned lanes, int te, int lean) {
     const dim3 grid((unsigned)((n_out + 127) / 128), lanes);
-    if (te) hipLaunchKernelGGL(k_reduce_level_p<TeOps>, grid, dim3(128), 0, st, P, E, n_in, L, scale_dbl, Po, Eo, n_out);
-    else hipLaunchKernelGGL(k_reduce_level_p<XyzzOps>, grid, dim3(128), 0, st, P, E, n_in, L, scale_dbl, Po, Eo, n_out);
+    if (!te) hipLaunchKernelGGL(k_reduce_level_p<XyzzOps>, grid, dim3(128), 0, st, P, E, n_in, L, scale_dbl, Po, Eo, n_out);
+    else if (!(lean & 1)) hipLaunchKernelGGL(k_reduce_level_p<TeOps>, grid, dim3(128), 0, st, P, E, n_in, L, scale_dbl, Po, Eo, n_out);
+    else if (lean & 2) hipLaunchKernelGGL((k_reduce_level_p<TeOps, 3>), grid, dim3(128), 0, st, P, E, n_in, L, scale_dbl, Po, Eo, n_out);
+    else hipLaunchKernelGGL((k_reduce_level_p<TeOps, 1>), grid, dim3(128), 0, st, P, E, n_in, L, scale_dbl, Po, Eo, n_out);
 }
 void launch_finish_g1_u(hipStream_t st, const u64* P, const u64* E, size_t segs, u64* out, int te) {
     const dim3 grid((unsigned)((segs + 63) / 64));
@@ -129,9 +133,10 @@ void launch_finish_g1_u(hipStream_t st, const u64* P, const u64* E, size_t segs,
     else hipLaunchKernelGGL(k_finish_p<XyzzOps>, grid, dim3(64), 0, st, P, E, segs, out);
 }
 void launch_reduce_tail_g1_u(hipStream_t st, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl, u64* scratch, u64* sums, u64* out, unsigned lanes,
-                             int te) {
+                             int te, int lean) {
     if (te) {
-        hipLaunchKernelGGL(k_reduce_tail_sums_p<TeOps>, dim3(TAIL_BLOCKS, lanes), dim3(TAIL_THREADS), 0, st, P, E, n_in, scratch, sums);
+        if (lean & 1) hipLaunchKernelGGL((k_reduce_tail_sums_p<TeOps, 1>), dim3(TAIL_BLOCKS, lanes), dim3(TAIL_THREADS), 0, st, P, E, n_in, scratch, sums);
+        else hipLaunchKernelGGL(k_reduce_tail_sums_p<TeOps>, dim3(TAIL_BLOCKS, lanes), dim3(TAIL_THREADS), 0, st, P, E, n_in, scratch, sums);
         hipLaunchKernelGGL(k_reduce_tail_finish_p<TeOps>, dim3((lanes + 63) / 64), dim3(64), 0, st, sums, scale_dbl, (size_t)lanes, out);
     } else {
         hipLaunchKernelGGL(k_reduce_tail_sums_p<XyzzOps>, dim3(TAIL_BLOCKS, lanes), dim3(TAIL_THREADS), 0, st, P, E, n_in, scratch, sums);

@@ -122,6 +122,27 @@ __device__ __forceinline__ void teu_add(TEU& a, const TEU& b) {
     }
     teu_finish(a, fqu_sub_lazy<4>(B, A), F, G, fqu_add_lazy(B, A));
 }
+// kT = 2 D T of a point that is an operand of more than one addition (the running sum of the bucket reduction: addend of A += running and
+// accumulator of the next running += P), computed once.  t: a multiply output or a loaded coordinate (normalised), 2 D canonical: kT is
+// a multiply output, < 1.01 p, normalised.
+__device__ __forceinline__ FqU teu_kt(const TEU& b) { return fqu_mul(b.t, te_2d_u()); }
+// a += b with kTb = teu_kt(b): teu_add with C = T1 (2 D T2) instead of (T1 T2) 2 D, 8M.  Both factors of C are normalised (a.t: a
+// multiply output or a loaded coordinate; kTb: a multiply output), so C is a multiply output below 1.01 p exactly as in teu_add, and
+// F = D - C + 4 p, G = D + C keep their bounds (limbs < 2^30).  The same residue as teu_add's C, not always the same representative.
+__device__ __forceinline__ void teu_add_kt(TEU& a, const TEU& b, const FqU& kTb) {
+    const FqU A = fqu_mul(fqu_sub_lazy<8>(a.y, a.x), fqu_sub_lazy<8>(b.y, b.x));
+    const FqU B = fqu_mul(fqu_add_lazy(a.y, a.x), fqu_add_lazy(b.y, b.x));
+    const FqU C = fqu_mul(a.t, kTb);
+    const FqU Dh = fqu_mul(a.z, b.z);
+    FqU F, G;
+#pragma unroll
+    for (int i = 0; i < 14; i++) {
+        const u32 d = Dh.l[i] + Dh.l[i];
+        F.l[i] = d + (fqu_4p(i) - C.l[i]);
+        G.l[i] = d + C.l[i];
+    }
+    teu_finish(a, fqu_sub_lazy<4>(B, A), F, G, fqu_add_lazy(B, A));
+}
 // a = 2 a (dbl-2008-hwcd with a = -1: 4M + 4S)
 __device__ __forceinline__ void teu_double(TEU& a) {
     const FqU A = fqu_sqr(a.x), B = fqu_sqr(a.y), Cz = fqu_sqr(a.z);
@@ -183,11 +204,12 @@ __device__ __forceinline__ void te_store_coord(u64* p, const FqU& v) {
 // `neg` adds -P = (-X, Y): the roles of Y - X and Y + X swap, 2 D X Y changes sign.  (Grouping a bucket's entries by sign so that the
 // sign could be compiled into two loops was tried: the lanes of a wave then run max(#positive) + max(#negative) iterations instead of
 // max(#entries) -- 8.76 against 7.98 ms per launch.)
+// The swap is made on the two ADDRESSES, before the loads: the coordinates are separate 64-byte sectors gathered per thread anyway, and
+// a swap of the loaded values is 28 v_cndmask_b32 per addition.
 __device__ __forceinline__ void te_load_niels(const u64* pp, bool neg, FqU& ym, FqU& yp, FqU& k2) {
-    const FqU a = te_load_coord(pp), b = te_load_coord(pp + 8);
+    ym = te_load_coord(pp + (neg ? 8 : 0));
+    yp = te_load_coord(pp + (neg ? 0 : 8));
     k2 = te_load_coord(pp + 16);
-    ym = neg ? b : a;
-    yp = neg ? a : b;
     if (neg) {
 #pragma unroll
         for (int i = 0; i < 14; i++) k2.l[i] = fqu_4p(i) - k2.l[i];      // 4 p - k, lazy

@@ -132,6 +132,9 @@ const char* czk_version(void);
  *   "msm_sort_onepass" 0/1      single-pass digit sort for every call (default: never -- the partitioned sort)
  *   "msm_fixed_c" 0/1           keys registered AFTERWARDS keep their own window width for short calls (no secondary table sets)
  *   "msm_window_g1" / "msm_window_g2" 0, 8..22   primary window width of keys registered AFTERWARDS (0 = the cost model, default)
+ *   "msm_reduce_lean" 0..3      a bit set (default 3) for the bucket reduction of keys in twisted Edwards form: 1 = its running sums start from the entries themselves
+ *                               instead of the neutral element, 2 = (with 1) one 2 D T product serves both additions a running sum takes part in; a clear bit = the
+ *                               same group element from the kernel of before (the Jacobian triple of a result may differ by a projective factor)
  *   "ntt_gen1" 0/1              first-generation NTT passes (the small-domain kernels) for every size
  *   "ntt_fuse_pairs" 0/1        czk_witness_map_pre/post: the last pass of an inverse transform and the first pass of the coset transform that follows it
  *                               as one kernel where their tiles line up (2^21, 2^18, 2^15, 2^14, 2^12); same values; default 0 (+ 0.5 % per proof measured)
