@@ -28,8 +28,19 @@ CZK_G1, CZK_G2 = 1, 2
 CZK_OP_ADD, CZK_OP_SUB, CZK_OP_MUL = 0, 1, 2
 CZK_NET_RCCL, CZK_NET_SHM, CZK_NET_IPC = 1, 2, 3
 CZK_OPEN_COMMIT = 1
+CZK_OPEN_COMMIT_TREE = 2
+CZK_COMMIT_LEAF_ELEMS, CZK_COMMIT_FANOUT = 32, 32   # czk.h "czk tree commitment v1": elements per leaf, digests per node
 CZK_ERR_NET, CZK_ERR_CHECK = 5, 6
 _STATUS = {1: "CZK_ERR_SIZE", 2: "CZK_ERR_HIP", 3: "CZK_ERR_ARG", 4: "CZK_ERR_NOMEM", 5: "CZK_ERR_NET", 6: "CZK_ERR_CHECK"}
+
+
+def open_commit_flags(commit) -> int:
+    """commit = True | False | "tree" -> the flags of czk_spdz_batch_open"""
+    if isinstance(commit, str):
+        if commit != "tree":
+            raise ValueError(f"commit must be True, False or 'tree', not {commit!r}")
+        return CZK_OPEN_COMMIT | CZK_OPEN_COMMIT_TREE
+    return CZK_OPEN_COMMIT if commit else 0
 
 
 class CzkError(RuntimeError):
@@ -352,6 +363,23 @@ class Context:
             n = a.size // 4
         out = np.zeros(8 + 32 * n, dtype=np.uint8)
         self._ck(self._L.czk_fr_vec_serialize(self._h, _ptr(a if n else None), C.c_size_t(n), C.c_int(mem), _ptr(out)))
+        return out.tobytes()
+
+    def fr_vec_commit(self, a, rand32: bytes, lanes: int = 1, n=None, stride=None, mem=CZK_MEM_HOST) -> bytes:
+        """czk.h "czk tree commitment v1" of `lanes` vectors of n Montgomery Fr, `stride` elements apart, hashed on the GPU: lanes x 32 bytes.
+        rand32: lanes x 32 bytes.  Host mode: a is (lanes, n, 4) / (n, 4) limbs (n and stride from its shape unless given); device mode: a pointer."""
+        if mem == CZK_MEM_HOST and a is not None:
+            a = np.ascontiguousarray(a, np.uint64)
+            if n is None:
+                n = a.size // (4 * lanes) if lanes else 0
+        n = 0 if n is None else n
+        stride = n if stride is None else stride
+        rnd = np.frombuffer(bytes(rand32), dtype=np.uint8)
+        if rnd.size != 32 * lanes:
+            raise ValueError("rand32 must hold 32 bytes per lane")
+        out = np.zeros(32 * lanes, dtype=np.uint8)
+        self._ck(self._L.czk_fr_vec_commit(self._h, _ptr(a if (n and lanes) else None), C.c_size_t(lanes), C.c_size_t(n), C.c_size_t(stride),
+                                           _ptr(rnd if lanes else None), _ptr(out if lanes else None), C.c_int(mem)))
         return out.tobytes()
 
     def fr_vec_deserialize(self, data: bytes, out=None, cap=None, mem=CZK_MEM_HOST):
@@ -1000,18 +1028,22 @@ class Net:
         self._ck(self._L.czk_net_recv_from_king(self._h, _ptr(send if nbytes else None), C.c_size_t(nbytes), _ptr(recv if nbytes else None), C.c_int(mem)))
         return recv
 
-    def atomic_broadcast(self, x_ptr, n: int, recv_ptr, rand32: bytes | None = None, mem: int = CZK_MEM_DEVICE):
+    def atomic_broadcast(self, x_ptr, n: int, recv_ptr, rand32: bytes | None = None, mem: int = CZK_MEM_DEVICE, tree: bool = False):
+        """tree=True: the commitment is czk.h's tree commitment, hashed on the GPU (all ranks must choose alike)"""
         r = (C.c_uint8 * 32).from_buffer_copy(rand32) if rand32 is not None else None
-        self._ck(self._L.czk_net_atomic_broadcast(self._h, _ptr(x_ptr), C.c_size_t(n), _ptr(recv_ptr), r, C.c_int(mem)))
+        fn = self._L.czk_net_atomic_broadcast_tree if tree else self._L.czk_net_atomic_broadcast
+        self._ck(fn(self._h, _ptr(x_ptr), C.c_size_t(n), _ptr(recv_ptr), r, C.c_int(mem)))
 
     # ---- the reference's batch opens on device lanes ---------------------------------------------------------------------------
-    def spdz_batch_open(self, sh_ptr, mac_ptr, mac_share, n: int, out_ptr, commit: bool = True) -> int:
+    def spdz_batch_open(self, sh_ptr, mac_ptr, mac_share, n: int, out_ptr, commit: bool | str = True) -> int:
         """SpdzFieldShare::batch_open; returns the number of failed MAC checks (the reference asserts 0).  commit=True (the default, as in the
-        reference: spdz.rs:179 -> channel.rs:50-75) sends dx_ts through the commit-then-open round; False is an explicit opt-out."""
+        reference: spdz.rs:179 -> channel.rs:50-75) sends dx_ts through the commit-then-open round; False is an explicit opt-out; "tree" = the
+        round with the tree commitment hashed on the GPU."""
+        flags = open_commit_flags(commit)
         ms = np.ascontiguousarray(mac_share, np.uint64).reshape(4)
         bad = C.c_uint64(0)
         self._ck(self._L.czk_spdz_batch_open(self._h, _ptr(sh_ptr), _ptr(mac_ptr), _ptr(ms), C.c_size_t(n), _ptr(out_ptr),
-                                             C.c_int(CZK_OPEN_COMMIT if commit else 0), C.byref(bad)))
+                                             C.c_int(flags), C.byref(bad)))
         return bad.value
 
     def add_batch_open(self, val_ptr, n: int, out_ptr):

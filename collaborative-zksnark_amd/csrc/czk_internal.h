@@ -331,6 +331,8 @@ inline int drop_table_pair(czk_ctx* ctx, T** a, T** b, hipError_t e) {
 void xfer_destroy(czk_ctx* ctx);
 int upload_pageable(czk_ctx* ctx, void* dev, const void* host, size_t bytes);
 int download_pageable(czk_ctx* ctx, void* host, const void* dev, size_t bytes);
+// implemented in commit_tree.hip: the tree commitments (czk.h "czk tree commitment v1") of `lanes` DEVICE vectors; rand32 / out32: lanes x 32 bytes, host.  Blocking.
+int commit_tree_device(czk_ctx* ctx, const u64* a, size_t lanes, size_t n, size_t stride, const uint8_t* rand32, uint8_t* out32);
 // implemented in ntt.hip
 // `addend` (lanes x D canonical Fr, not the lanes being transformed) rides on the last pass's store: a coset inverse transform writes
 // (coset_ifft(data) - addend) * *scale, a forward or coset forward transform writes its output + addend (scale unused).  Same values as the pointwise kernels.

@@ -30,70 +30,12 @@
 #include <cstring>
 
 #include "czk_internal.h"
+#include "sha256.h"
 
 using namespace czk;
 
-// ---- SHA-256 (FIPS 180-4): the reference's CommitHash (mpc-algebra/src/channel.rs:92) ---------------------------------------------
+// (SHA-256, the reference's CommitHash of mpc-algebra/src/channel.rs:92: sha256.h)
 namespace {
-struct Sha256 {
-    uint32_t h[8];
-    uint8_t buf[64];
-    uint64_t len = 0;
-    size_t fill = 0;
-    Sha256() {
-        static const uint32_t iv[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-        memcpy(h, iv, sizeof h);
-    }
-    static uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-    void block(const uint8_t* p) {
-        static const uint32_t K[64] = {
-            0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u, 0x243185beu,
-            0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau,
-            0x5cb0a9dcu, 0x76f988dau, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u, 0x27b70a85u,
-            0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u, 0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u,
-            0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu,
-            0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-        uint32_t w[64];
-        for (int i = 0; i < 16; i++) w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
-        for (int i = 16; i < 64; i++) {
-            const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-            w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-        }
-        uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-        for (int i = 0; i < 64; i++) {
-            const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + K[i] + w[i];
-            const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-            hh = g, g = f, f = e, e = d + t1, d = c, c = b, b = a, a = t1 + t2;
-        }
-        h[0] += a, h[1] += b, h[2] += c, h[3] += d, h[4] += e, h[5] += f, h[6] += g, h[7] += hh;
-    }
-    void update(const void* data, size_t n) {
-        const uint8_t* p = (const uint8_t*)data;
-        len += n;
-        if (fill) {
-            const size_t take = n < 64 - fill ? n : 64 - fill;
-            memcpy(buf + fill, p, take);
-            fill += take, p += take, n -= take;
-            if (fill < 64) return;
-            block(buf);
-            fill = 0;
-        }
-        for (; n >= 64; p += 64, n -= 64) block(p);
-        if (n) memcpy(buf, p, n), fill = n;
-    }
-    void finish(uint8_t* out32) {
-        const uint64_t bits = len * 8;
-        const uint8_t one = 0x80, zero = 0;
-        update(&one, 1);
-        while (fill != 56) update(&zero, 1);
-        uint8_t be[8];
-        for (int i = 0; i < 8; i++) be[i] = (uint8_t)(bits >> (56 - 8 * i));
-        update(be, 8);
-        for (int i = 0; i < 8; i++)
-            for (int j = 0; j < 4; j++) out32[4 * i + j] = (uint8_t)(h[i] >> (24 - 8 * j));
-    }
-};
-
 double now_ms() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -825,6 +767,30 @@ extern "C" int czk_net_atomic_broadcast(czk_net* n, const uint64_t* x, size_t cn
     return CZK_OK;
 }
 
+// The same round with the tree commitment of commit_tree.hip: the same three exchanges with the same byte counts (a rank that made the SHA-256 call instead
+// meets this one in every exchange, and both fail the check), the same stats; the W gathered vectors are hashed in one pass on the device.
+extern "C" int czk_net_atomic_broadcast_tree(czk_net* n, const uint64_t* x, size_t cnt, uint64_t* recv, const uint8_t* rand32, int mem) {
+    if (!n) return CZK_ERR_ARG;
+    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "czk_net_atomic_broadcast_tree needs a communicator created with a context");
+    if (!valid_mem(mem)) return net_err(n, CZK_ERR_ARG, "czk_net: mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
+    if (cnt && (!x || !recv)) return net_err(n, CZK_ERR_ARG, "czk_net_atomic_broadcast_tree: null buffer");
+    const size_t W = (size_t)n->world;
+    std::vector<uint8_t> rnd(32), commit(32), all_commits(32 * W), all_rnd(32 * W), check(32 * W);
+    if (rand32) memcpy(rnd.data(), rand32, 32);
+    else if (getrandom(rnd.data(), 32, 0) != 32) return net_err(n, CZK_ERR_NET, "getrandom failed");
+    NET_CTX(n, czk_fr_vec_commit(n->ctx, x, 1, cnt, cnt, rnd.data(), commit.data(), mem));
+    CZK_TRY(exchange(n, Op::Broadcast, commit.data(), 32, all_commits.data(), CZK_MEM_HOST));   // exchange commitments
+    CZK_TRY(exchange(n, Op::Broadcast, x, 32 * cnt, recv, mem));                                 // exchange (data || randomness)
+    CZK_TRY(exchange(n, Op::Broadcast, rnd.data(), 32, all_rnd.data(), CZK_MEM_HOST));
+    count_stats(n, Op::Broadcast, 32);              // counted as the reference's two broadcasts (channel.rs:58-61), as czk_net_atomic_broadcast does
+    count_stats(n, Op::Broadcast, 8 + 32 * cnt + 32);
+    NET_CTX(n, czk_fr_vec_commit(n->ctx, recv, W, cnt, cnt, all_rnd.data(), check.data(), mem));   // (waits for the gathered vectors: stream order)
+    for (size_t p = 0; p < W; p++)
+        if ((int)p != n->rank && memcmp(&check[32 * p], &all_commits[32 * p], 32) != 0)
+            return net_err(n, CZK_ERR_CHECK, "atomic_broadcast: party " + std::to_string(p) + "'s data does not match its commitment");
+    return CZK_OK;
+}
+
 namespace {
 int open_args(czk_net* n, const void* a, const void* b, size_t cnt) {
     if (!n) return CZK_ERR_ARG;
@@ -849,7 +815,8 @@ extern "C" int czk_spdz_batch_open(czk_net* n, const uint64_t* sh, const uint64_
     CZK_TRY(czk_net_broadcast(n, sh, cnt * 32, g, CZK_MEM_DEVICE));                       // let all_vals = Net::broadcast(&s_vals)
     NET_CTX(n, czk_fr_lanes_sum(n->ctx, g, W, cnt, out_value, nullptr));                  // vals[i] = sum over the parties
     NET_CTX(n, czk_fr_spdz_dx(n->ctx, out_value, mac, mac_share, dx, cnt));               // dx_t = mac_share * val - mac
-    if (flags & CZK_OPEN_COMMIT) CZK_TRY(czk_net_atomic_broadcast(n, dx, cnt, g, nullptr, CZK_MEM_DEVICE));   // Net::atomic_broadcast(&dx_ts)
+    if (flags & CZK_OPEN_COMMIT_TREE) CZK_TRY(czk_net_atomic_broadcast_tree(n, dx, cnt, g, nullptr, CZK_MEM_DEVICE));
+    else if (flags & CZK_OPEN_COMMIT) CZK_TRY(czk_net_atomic_broadcast(n, dx, cnt, g, nullptr, CZK_MEM_DEVICE));   // Net::atomic_broadcast(&dx_ts)
     else CZK_TRY(czk_net_broadcast(n, dx, cnt * 32, g, CZK_MEM_DEVICE));
     NET_CTX(n, czk_fr_lanes_sum(n->ctx, g, W, cnt, nullptr, out_bad));                    // assert!(sum.is_zero()) -- the caller's, on *out_bad
     return CZK_OK;

@@ -309,13 +309,15 @@ def deserialize_fr_vec(buf: bytes):
     return np.frombuffer(buf[8:], dtype="<u8").reshape(n, 4).astype(np.uint64)
 
 
-def atomic_broadcast(ctx, x: torch.Tensor, rand32: bytes | None = None) -> torch.Tensor:
+def atomic_broadcast(ctx, x: torch.Tensor, rand32: bytes | None = None, tree: bool = False) -> torch.Tensor:
     """mpc-algebra/src/channel.rs:50-75 `atomic_broadcast` of one Fr vector (device tensor, Montgomery limbs): every party first
     broadcasts SHA-256(serialized vector || 32 random bytes), then the data itself; each receiver re-hashes what the others
     sent and compares (commit-then-open: nobody can choose its vector after seeing the others').  Returns the gathered
     vectors (world, n, 4).  The commitment runs over the reference's wire bytes (canonical limbs with a u64 length prefix), so
     the hashes equal the reference's for equal data and randomness.  Host-side hashing: this is the protocol's check, not hot-path
-    arithmetic; pass commit=False to spdz_batch_open to skip it."""
+    arithmetic; pass commit=False to spdz_batch_open to skip it.  tree=True commits with the library's SHA-256 tree instead (czk.h "czk tree
+    commitment v1", Context.fr_vec_commit): hashed on the GPU over the device tensors, only digests reach the host; for parties that are all
+    this library -- these are not the reference's bytes."""
     import hashlib
     import os as _os
     import numpy as np
@@ -326,12 +328,26 @@ def atomic_broadcast(ctx, x: torch.Tensor, rand32: bytes | None = None) -> torch
         data = torch.empty((world,) + tuple(x.shape), dtype=x.dtype, device=x.device)
         _net_in(ctx, x)
         try:
-            _NET.atomic_broadcast(x.data_ptr(), n, data.data_ptr(), rand32=rand32)
+            _NET.atomic_broadcast(x.data_ptr(), n, data.data_ptr(), rand32=rand32, tree=tree)
         except Exception as e:
             if getattr(e, "code", None) == 6:            # CZK_ERR_CHECK
                 raise MpcCheckError(str(e)) from e
             raise
         return _after_consume(ctx, data)
+    if tree:
+        x = x.contiguous()
+        rnd = rand32 if rand32 is not None else _os.urandom(COMMIT_RAND_BYTES)
+        dev = x.device
+        digest = ctx.fr_vec_commit(x.data_ptr(), rnd, lanes=1, n=n, mem=1)
+        commits = all_gather_shares(torch.frombuffer(bytearray(digest), dtype=torch.uint8).to(dev))          # the same three rounds as below
+        data = all_gather_shares(x, ctx).contiguous()
+        rnds = all_gather_shares(torch.frombuffer(bytearray(rnd), dtype=torch.uint8).to(dev))
+        check = ctx.fr_vec_commit(data.data_ptr(), bytes(rnds.cpu().numpy()), lanes=world, n=n, stride=n, mem=1)   # every party's vector in one pass
+        commits = bytes(commits.cpu().numpy())
+        for p in range(world):
+            if p != rank and check[32 * p:32 * p + 32] != commits[32 * p:32 * p + 32]:
+                raise MpcCheckError(f"atomic_broadcast: party {p}'s data does not match its commitment")
+        return data
     rep = torch.empty_like(x)
     ctx.fr_into_repr(x.data_ptr(), out=rep.data_ptr(), n=n, mem=1)
     ctx.sync()
@@ -354,10 +370,13 @@ def atomic_broadcast(ctx, x: torch.Tensor, rand32: bytes | None = None) -> torch
     return data
 
 
-def spdz_batch_open(ctx, sh: torch.Tensor, mac: torch.Tensor, mac_share, commit: bool = True) -> torch.Tensor:
+def spdz_batch_open(ctx, sh: torch.Tensor, mac: torch.Tensor, mac_share, commit: bool | str = True) -> torch.Tensor:
     """SpdzFieldShare::batch_open as the reference runs it with one process per party (mpc-algebra/src/share/spdz.rs:166-185):
     round 1 broadcast of the `sh` lanes and their sum; dx_t = mac_share * value - mac; round 2 atomic_broadcast of dx_t, whose
-    sum must vanish.  MAC shares themselves never leave the party.  sh, mac: (n, 4) device tensors; mac_share: (4,) uint64."""
+    sum must vanish.  MAC shares themselves never leave the party.  sh, mac: (n, 4) device tensors; mac_share: (4,) uint64.
+    commit: True (SHA-256 over the wire bytes, the reference's), False (no commit round) or "tree" (atomic_broadcast(tree=True))."""
+    if isinstance(commit, str) and commit != "tree":
+        raise ValueError(f"commit must be True, False or 'tree', not {commit!r}")
     world, _ = _world_rank()
     n = sh.shape[0]
     if _NET is not None and sh.is_cuda:                                     # one C-ABI call: czk_spdz_batch_open
@@ -378,7 +397,7 @@ def spdz_batch_open(ctx, sh: torch.Tensor, mac: torch.Tensor, mac_share, commit:
     ctx.fr_lanes_sum(gathered.data_ptr(), world, n, out_ptr=vals.data_ptr())
     dx = torch.empty_like(sh)
     ctx.fr_spdz_dx(vals.data_ptr(), mac.data_ptr(), mac_share, dx.data_ptr(), n)
-    all_dx = atomic_broadcast(ctx, dx) if commit else all_gather_shares(dx, ctx)   # Net::atomic_broadcast(&dx_ts)
+    all_dx = atomic_broadcast(ctx, dx, tree=commit == "tree") if commit else all_gather_shares(dx, ctx)   # Net::atomic_broadcast(&dx_ts)
     bad = ctx.fr_lanes_sum(all_dx.contiguous().data_ptr(), world, n, count_nonzero=True)
     if bad != 0:                                                            # assert!(sum.is_zero())
         raise MpcCheckError(f"SPDZ MAC check failed on {bad} of {n} opened values")

@@ -116,7 +116,7 @@ class Groth16Local:
         # enqueue order of the four MSMs that need no witness map.  The witness map only makes progress beside the G2 accumulate kernel (EXPERIMENTS.md
         # section 14); with that kernel second it is done closer to the moment `h` is needed: 14.51 / 14.54 against 14.42 / 14.29 proofs/s with b_g2 first
         self.msm_order = ("l", "b_g2", "a", "b_g1")
-        self.commit_opens = True                      # dx_t goes through atomic_broadcast (commit-then-open, spdz.rs:179, channel.rs:50-75); False = explicit opt-out
+        self.commit_opens = True                      # dx_t goes through atomic_broadcast (commit-then-open, spdz.rs:179, channel.rs:50-75); False = explicit opt-out; "tree" = the round with the tree commitment hashed on the GPU
         # mac_share() = 1 on the king, 0 elsewhere (share/spdz.rs:30-37: the reference's stand-in MAC key is 1)
         self.mac_share = to_mont_limbs([1 if (self.local and self.local[0] == 0) else 0])[0]
         self.lanes = self.lpp * len(self.local)       # SPDZ: sh + mac per party (share/spdz.rs:50-53); HBC: the additive share alone

@@ -334,8 +334,28 @@ int czk_net_barrier(czk_net* net);
  * work over a download of the vectors: the protocol's check, not hot-path arithmetic -- the opens below take it as an option. */
 int czk_net_atomic_broadcast(czk_net* net, const uint64_t* x, size_t n, uint64_t* recv, const uint8_t* rand32, int mem);
 
+/* "czk tree commitment v1": a second, opt-in commitment for the same round, computed on the GPU where the vector lives (commit_tree.hip).
+ * NOT the reference's bytes: for parties that are all this library (every czk_net transport), never for a party on the reference's sockets.
+ *   E = CZK_COMMIT_LEAF_ELEMS, F = CZK_COMMIT_FANOUT.  TAG_LEAF / TAG_NODE / TAG_ROOT = the ASCII strings "czk-commit-v1/leaf", "czk-commit-v1/node",
+ *   "czk-commit-v1/root", zero-padded to 64 bytes (one SHA-256 block each).  bytes(a_k) = into_repr() as 32 little-endian bytes (czk_fr_vec_serialize's).
+ *   leaf_i = SHA256(TAG_LEAF || bytes(a[i E]) .. bytes(a[min(n, (i + 1) E) - 1])), max(1, ceil(n / E)) leaves (n = 0: the one leaf is SHA256(TAG_LEAF));
+ *   node_j = SHA256(TAG_NODE || up to F consecutive digests of the level below), level by level until one digest `top` is left (one leaf: top = leaf_0);
+ *   commitment = SHA256(TAG_ROOT || u64_le(n) || top || rand32).
+ * czk_fr_vec_commit: a = `lanes` vectors of n Montgomery Fr, `stride` elements apart, in `mem` (host memory is uploaded and hashed by the same
+ * kernels); rand32 and out32: lanes x 32 bytes, HOST.  Blocks.  Reads a[lane][0..n) only.  stride < n or byte counts that overflow: CZK_ERR_SIZE;
+ * lanes = 0: CZK_OK, nothing touched; n = 0: the empty vector's commitment. */
+#define CZK_COMMIT_LEAF_ELEMS 32
+#define CZK_COMMIT_FANOUT 32
+int czk_fr_vec_commit(czk_ctx* ctx, const uint64_t* a, size_t lanes, size_t n, size_t stride, const uint8_t* rand32, uint8_t* out32, int mem);
+/* czk_net_atomic_broadcast with the tree commitment: same contract, rounds, byte counts and stats.  The receiver checks all `world` gathered vectors
+ * in one czk_fr_vec_commit pass (lanes = world, stride = n) and compares digests on the host: with CZK_MEM_DEVICE no element byte crosses to the host,
+ * only commitments, randomness and world x 32 digest bytes.  All ranks must make the same call: against a rank that used czk_net_atomic_broadcast
+ * nothing hangs (equal byte counts) and every honest rank gets CZK_ERR_CHECK. */
+int czk_net_atomic_broadcast_tree(czk_net* net, const uint64_t* x, size_t n, uint64_t* recv, const uint8_t* rand32, int mem);
+
 /* The reference's batch opens as ONE call each on device lanes (all buffers CZK_MEM_DEVICE on the communicator's context; gathered
- * shares live in the communicator's own scratch).  flags: CZK_OPEN_COMMIT = the second round goes through czk_net_atomic_broadcast.
+ * shares live in the communicator's own scratch).  flags: CZK_OPEN_COMMIT = the second round goes through czk_net_atomic_broadcast;
+ * CZK_OPEN_COMMIT_TREE (with or without CZK_OPEN_COMMIT) = through czk_net_atomic_broadcast_tree.
  *   czk_spdz_batch_open  SpdzFieldShare::batch_open (mpc-algebra/src/share/spdz.rs:166-185): broadcast of the sh lane, value = sum;
  *                        dx_t = mac_share * value - mac; (atomic_)broadcast of dx_t; *out_bad = number of i whose dx_t do not sum to
  *                        zero (the reference asserts 0).  sh, mac: n Fr each; mac_share: one Montgomery Fr, HOST (1 on the king, 0
@@ -345,6 +365,7 @@ int czk_net_atomic_broadcast(czk_net* net, const uint64_t* x, size_t n, uint64_t
  *                        the size-world inverse DFT, degree check, p(0); degrees / degree / out_bad as in czk_fr_gsz_open.
  * out_value may alias the input share lane.  Each call ends with the read-back of its check count (the reference asserts right there). */
 #define CZK_OPEN_COMMIT 1
+#define CZK_OPEN_COMMIT_TREE 2
 int czk_spdz_batch_open(czk_net* net, const uint64_t* sh, const uint64_t* mac, const uint64_t* mac_share, size_t n, uint64_t* out_value,
                         int flags, uint64_t* out_bad);
 int czk_add_batch_open(czk_net* net, const uint64_t* val, size_t n, uint64_t* out_value);

@@ -86,6 +86,14 @@ class Context {
     void reserve(unsigned ntt_log_d, size_t ntt_lanes, const czk_bases* bases = nullptr, size_t n_scalars = 0, size_t msm_lanes = 0) const {
         check(czk_ctx_reserve(ctx_, ntt_log_d, ntt_lanes, bases, n_scalars, msm_lanes));
     }
+    // czk_fr_vec_commit: the tree commitments (czk.h "czk tree commitment v1") of `lanes` vectors of n Montgomery Fr, `stride` elements apart, hashed on the
+    // GPU; rand32: 32 bytes per lane.  Returns 32 bytes per lane.
+    std::vector<uint8_t> fr_vec_commit(const uint64_t* a, size_t lanes, size_t n, size_t stride, const std::vector<uint8_t>& rand32, int mem) const {
+        if (rand32.size() != 32 * lanes) throw Panic(CZK_ERR_ARG, "fr_vec_commit: rand32 must hold 32 bytes per lane");
+        std::vector<uint8_t> out(32 * lanes);
+        check(czk_fr_vec_commit(ctx_, a, lanes, n, stride, rand32.data(), out.data(), mem));
+        return out;
+    }
 
   private:
     czk_ctx* ctx_ = nullptr;
@@ -137,6 +145,9 @@ class DeviceLanes {
   public:
     size_t len;   // logical Vec length of every lane (<= capacity)
 };
+
+// the commit round of the SPDZ open: none, the reference's SHA-256 over the wire bytes (host), or the tree commitment hashed on the GPU (all-czk parties only)
+enum class OpenCommit { None, Sha256, Tree };
 
 // mpc-net's MpcMultiNet for parties that are czk contexts (include/czk.h "mpc-net between GPUs"): the exchanges of an open run on the
 // context's stream, on lanes that stay in HBM.  One Net per (Context, party); destroy it before its Context.
@@ -208,6 +219,17 @@ class Net {
         uint64_t bad = 0;
         check(czk_spdz_batch_open(n_, shares.data(sh_lane), shares.data(sh_lane + 1), mac_share.l, n, out, commit ? CZK_OPEN_COMMIT : 0, &bad));
         if (bad) throw Panic(CZK_ERR_CHECK, "assertion failed: sum.is_zero() (SPDZ MAC check, share/spdz.rs:183) on " + std::to_string(bad) + " values");
+    }
+    void spdz_batch_open(const DeviceLanes& shares, size_t sh_lane, const Fr& mac_share, size_t n, uint64_t* out, OpenCommit commit) const {
+        const int flags = commit == OpenCommit::Tree ? CZK_OPEN_COMMIT | CZK_OPEN_COMMIT_TREE : commit == OpenCommit::Sha256 ? CZK_OPEN_COMMIT : 0;
+        uint64_t bad = 0;
+        check(czk_spdz_batch_open(n_, shares.data(sh_lane), shares.data(sh_lane + 1), mac_share.l, n, out, flags, &bad));
+        if (bad) throw Panic(CZK_ERR_CHECK, "assertion failed: sum.is_zero() (SPDZ MAC check, share/spdz.rs:183) on " + std::to_string(bad) + " values");
+    }
+    // czk_net_atomic_broadcast_tree: MpcSerNet::atomic_broadcast (channel.rs:50-75) of n Fr with the tree commitment; recv: n_parties() x n Fr.
+    // A vector that does not match its commitment panics (CZK_ERR_CHECK), like the reference's assert_eq!.  rand32: nullptr = drawn from the OS.
+    void atomic_broadcast_tree(const uint64_t* x, size_t n, uint64_t* recv, int mem = CZK_MEM_DEVICE, const uint8_t* rand32 = nullptr) const {
+        check(czk_net_atomic_broadcast_tree(n_, x, n, recv, rand32, mem));
     }
     //   AdditiveFieldShare::batch_open (share/add.rs:256-259)
     void add_batch_open(const uint64_t* val, size_t n, uint64_t* out) const { check(czk_add_batch_open(n_, val, n, out)); }

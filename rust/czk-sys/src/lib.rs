@@ -74,7 +74,10 @@ pub const CZK_POINT_NO_POINT: c_int = 3; // czk_point_status
 pub const CZK_POINT_NOT_ON_CURVE: c_int = 4; // czk_point_status
 pub const CZK_POINT_NOT_IN_SUBGROUP: c_int = 5; // czk_point_status
 pub const CZK_NET_UNIQUE_ID_BYTES: c_int = 128; // #define
+pub const CZK_COMMIT_LEAF_ELEMS: c_int = 32; // #define
+pub const CZK_COMMIT_FANOUT: c_int = 32; // #define
 pub const CZK_OPEN_COMMIT: c_int = 1; // #define
+pub const CZK_OPEN_COMMIT_TREE: c_int = 2; // #define
 
 #[link(name = "czk_hip")]
 extern "C" {
@@ -129,6 +132,8 @@ extern "C" {
     pub fn czk_net_recv_from_king(net: *mut czk_net, send: *const c_void, bytes: usize, recv: *mut c_void, mem: c_int) -> c_int;
     pub fn czk_net_barrier(net: *mut czk_net) -> c_int;
     pub fn czk_net_atomic_broadcast(net: *mut czk_net, x: *const u64, n: usize, recv: *mut u64, rand32: *const u8, mem: c_int) -> c_int;
+    pub fn czk_fr_vec_commit(ctx: *mut czk_ctx, a: *const u64, lanes: usize, n: usize, stride: usize, rand32: *const u8, out32: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_net_atomic_broadcast_tree(net: *mut czk_net, x: *const u64, n: usize, recv: *mut u64, rand32: *const u8, mem: c_int) -> c_int;
     pub fn czk_spdz_batch_open(net: *mut czk_net, sh: *const u64, mac: *const u64, mac_share: *const u64, n: usize, out_value: *mut u64, flags: c_int, out_bad: *mut u64) -> c_int;
     pub fn czk_add_batch_open(net: *mut czk_net, val: *const u64, n: usize, out_value: *mut u64) -> c_int;
     pub fn czk_gsz_batch_open(net: *mut czk_net, val: *const u64, n: usize, degrees: *const u32, degree: c_uint, out_value: *mut u64, out_bad: *mut u64) -> c_int;

@@ -693,6 +693,14 @@ pub mod net {
     // `CTX` mutex first, exactly like the transforms and MSMs of this crate; `party_id` / `n_parties` / `stats` only read the communicator's own fields.
     unsafe impl Send for Net {}
 
+    /// The commit round of the SPDZ open: none, the reference's SHA-256 over the wire bytes, or the tree commitment hashed on the GPU.
+    #[derive(Debug, Clone, Copy, PartialEq, Eq)]
+    pub enum OpenCommit {
+        None,
+        Sha256,
+        Tree,
+    }
+
     /// mpc-net/src/lib.rs `Stats`
     #[derive(Debug, Default, Clone, Copy)]
     pub struct Stats {
@@ -774,6 +782,22 @@ pub mod net {
                 sys::czk_spdz_batch_open(self.raw, shares.data(0, 0), shares.data(1, 0), ms.as_ptr(), n, out.data(0, 0),
                                          if commit { sys::CZK_OPEN_COMMIT } else { 0 }, &mut bad)
             };
+            self.expect(rc, "czk_spdz_batch_open");
+            assert!(bad == 0, "assertion failed: sum.is_zero() (SPDZ MAC check on {} values)", bad);
+        }
+        /// The same open with the commit round named: `OpenCommit::Tree` commits with the library's SHA-256 tree, hashed on the GPU (czk.h "czk tree
+        /// commitment v1") -- for parties that are all this library, never for a party on the reference's sockets.
+        pub fn spdz_batch_open_with(&self, shares: &DeviceLanes, mac_share: &Fr, n: usize, out: &mut DeviceLanes, commit: OpenCommit) {
+            let flags = match commit {
+                OpenCommit::None => 0,
+                OpenCommit::Sha256 => sys::CZK_OPEN_COMMIT,
+                OpenCommit::Tree => sys::CZK_OPEN_COMMIT | sys::CZK_OPEN_COMMIT_TREE,
+            };
+            let mut ms = [0u64; 4];
+            super::limbs::fr_to(mac_share, &mut ms);
+            let mut bad = 0u64;
+            let _ctx = CTX.lock().unwrap();   // the communicator enqueues on the shared context's stream and uses its staging buffers
+            let rc = unsafe { sys::czk_spdz_batch_open(self.raw, shares.data(0, 0), shares.data(1, 0), ms.as_ptr(), n, out.data(0, 0), flags, &mut bad) };
             self.expect(rc, "czk_spdz_batch_open");
             assert!(bad == 0, "assertion failed: sum.is_zero() (SPDZ MAC check on {} values)", bad);
         }

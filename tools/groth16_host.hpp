@@ -168,6 +168,7 @@ class Groth16Host {
     size_t N, P, L, D;
     unsigned log_d = 0;
     double register_s = 0, setup_s = 0;
+    bool tree_commit_opens = false;   // with commit_opens: the commit round uses the tree commitment hashed on the GPU (czk::OpenCommit::Tree), not SHA-256 over a download
 
     // local_parties: the MPC parties whose share lanes live on this GPU (empty = all of them, BASELINE configs[1]).  With ONE local
     // party and a czk::Net this is the reference's own layout -- one process per party (mpc-net/src/multi.rs:15-23) -- and the two opens
@@ -363,7 +364,8 @@ class Groth16Host {
     void open(const czk::DeviceLanes& shares, czk::DeviceLanes& out, uint64_t* chk) {
         const int M = CZK_MEM_DEVICE;
         if (local_.size() < P) {   // one party per process: Net::broadcast(&s_vals), dx_t, Net::atomic_broadcast(&dx_ts), assert (spdz.rs:166-185)
-            net_->spdz_batch_open(shares, 0, mac_share_, D, out.data(), commit_opens_);
+            net_->spdz_batch_open(shares, 0, mac_share_, D, out.data(),
+                                  !commit_opens_ ? czk::OpenCommit::None : tree_commit_opens ? czk::OpenCommit::Tree : czk::OpenCommit::Sha256);
             return;
         }
         ctx.check(czk_fr_vec_op(ctx.raw(), CZK_OP_ADD, shares.data(0), shares.data(2), out.data(), D, M));

@@ -209,7 +209,7 @@ static int bench(const Context& ctx, int argc, char** argv) {
 }
 
 // `host_demo.bin party --rank R --world W --id HEX [--transport shm|rccl] [--device D] [--log-n K | --constraints N] [--steps K]
-// [--warmup W] [--no-tables] [--no-commit-opens] [--exchange ring|p2p]`: ONE MPC party of the reference's own layout -- one process per
+// [--warmup W] [--no-tables] [--no-commit-opens | --tree-commit-opens] [--exchange ring|p2p]`: ONE MPC party of the reference's own layout -- one process per
 // party (mpc-net/src/multi.rs:15-23) -- as a compiled host: party R's two share lanes on this process's GPU, the two opens of every
 // witness map as SpdzFieldShare::batch_open through czk::Net (RCCL between GPUs; shared memory when the parties share a GPU), nothing
 // leaves HBM except the proof's group elements.  Rank 0 prints one JSON line whose results_sha256 covers ALL parties' elements in
@@ -219,6 +219,7 @@ static int party(int argc, char** argv) {
     size_t n = (size_t)1 << 20, steps = 4, warmup = 1;
     int rank = -1, world = 0, device = -1, transport = CZK_NET_SHM, exchange = 0;
     bool no_tables = false, commit = true;   // dx_ts through atomic_broadcast, as the reference does (spdz.rs:179); --no-commit-opens is the reported opt-out
+    bool tree = false;                       // --tree-commit-opens: the commit round with the tree commitment hashed on the GPU (reported as commit_hash: tree)
     std::vector<uint8_t> id;
     for (int i = 2; i < argc; i++) {
         auto val = [&]() -> const char* { return i + 1 < argc ? argv[++i] : "0"; };
@@ -234,7 +235,8 @@ static int party(int argc, char** argv) {
         else if (!strcmp(argv[i], "--exchange")) exchange = !strcmp(val(), "p2p") ? 1 : 0;
         else if (!strcmp(argv[i], "--no-tables")) no_tables = true;
         else if (!strcmp(argv[i], "--commit-opens")) commit = true;
-        else if (!strcmp(argv[i], "--no-commit-opens")) commit = false;
+        else if (!strcmp(argv[i], "--no-commit-opens")) commit = false, tree = false;
+        else if (!strcmp(argv[i], "--tree-commit-opens")) commit = true, tree = true;
         else { printf("unknown argument %s\n", argv[i]); return 2; }
     }
     if (rank < 0 || world < 2 || rank >= world || id.empty() || n < 2 || steps < 1) { printf("party: need --rank, --world >= 2, --id\n"); return 2; }
@@ -245,6 +247,7 @@ static int party(int argc, char** argv) {
     Net net(ctx, transport, rank, world, id);
     net.set_option("exchange", exchange);
     g16::Groth16Host prover(ctx, n, (size_t)world, 0xC0FFEE, no_tables, {(size_t)rank}, &net, commit);
+    prover.tree_commit_opens = tree;
     for (size_t i = 0; i < warmup; i++) prover.step();
     prover.results.clear();
     net.reset_stats();
@@ -273,11 +276,11 @@ static int party(int argc, char** argv) {
     czk_sha256(ordered.data(), ordered.size(), digest);
     printf("{\"harness\": \"tools/host_demo.cpp party (C++ over include/czk.hpp: one process per MPC party, opens through czk_net)\", \"layout\": \"party\", "
            "\"transport\": \"%s\", \"exchange\": \"%s\", \"constraints\": %zu, \"parties\": %d, \"share_lanes_per_process\": %zu, \"steps\": %zu, "
-           "\"warmup\": %zu, \"ms_per_proof\": %.4f, \"proofs_per_s\": %.5f, \"window_tables\": %s, \"commit_opens\": %s, \"pipelined_proofs_equal\": true, "
+           "\"warmup\": %zu, \"ms_per_proof\": %.4f, \"proofs_per_s\": %.5f, \"window_tables\": %s, \"commit_opens\": %s, \"commit_hash\": %s, \"pipelined_proofs_equal\": true, "
            "\"king_net_stats\": {\"bytes_sent\": %llu, \"bytes_recv\": %llu, \"broadcasts\": %llu, \"to_king\": %llu, \"from_king\": %llu}, "
            "\"results_sha256\": \"%s\"}\n",
            transport_name(transport), exchange ? "p2p" : "ring", prover.N, world, L, steps, warmup, dt / steps * 1e3, steps / dt,
-           no_tables ? "false" : "true", commit ? "true" : "false", (unsigned long long)st.bytes_sent, (unsigned long long)st.bytes_recv,
+           no_tables ? "false" : "true", commit ? "true" : "false", commit ? (tree ? "\"tree\"" : "\"sha256\"") : "null", (unsigned long long)st.bytes_sent, (unsigned long long)st.bytes_recv,
            (unsigned long long)st.broadcasts, (unsigned long long)st.to_king, (unsigned long long)st.from_king, hex(digest, 32).c_str());
     return 0;
 }
@@ -345,14 +348,15 @@ static int polyiop(const char* workload, int argc, char** argv) {
     double arena_gb = 0;
     const char* dump = nullptr;
     int rank = -1, world = 0, transport = CZK_NET_SHM, device = 0;
-    bool commit_opens = true, breakdown = false;
+    bool commit_opens = true, tree_commit_opens = false, breakdown = false;
     double stagger_ms = 0;   // several proofs in flight: prover k starts k * stagger_ms late, so that the provers are not all in the same round at the same time
     std::vector<std::pair<std::string, long>> ctx_options;
     std::vector<uint8_t> id;
     for (int i = 2; i < argc; i++) {
         auto val = [&]() -> const char* { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "--log-n")) n = (size_t)1 << atoi(val());
-        else if (!strcmp(argv[i], "--no-commit-opens")) commit_opens = false;
+        else if (!strcmp(argv[i], "--no-commit-opens")) commit_opens = false, tree_commit_opens = false;
+        else if (!strcmp(argv[i], "--tree-commit-opens")) commit_opens = true, tree_commit_opens = true;
         else if (!strcmp(argv[i], "--breakdown")) breakdown = true;
         else if (!strcmp(argv[i], "--stagger-ms")) stagger_ms = atof(val());
         else if (!strcmp(argv[i], "--ctx-option")) {   // NAME=VALUE: czk_ctx_set_option on every context before its first MSM (repeatable)
@@ -443,6 +447,7 @@ static int polyiop(const char* workload, int argc, char** argv) {
             M.net = net.get();
             M.net_gsz = plonk;
             M.commit_opens = commit_opens;
+            M.tree_commit_opens = tree_commit_opens;
             M.gsz_degree = (unsigned)((parties - 1) / 2);              // t = (n - 1) / 2 (share/gsz20/mod.rs:94-96)
             M.mac_share = rank == 0 ? pvm::fr_one() : pvm::fr_zero();   // mac_share() = 1 on the king, 0 elsewhere (share/spdz.rs:30-37)
         }
@@ -566,11 +571,12 @@ static int polyiop(const char* workload, int argc, char** argv) {
     printf("{\"harness\": \"tools/host_demo.cpp %s (C++ over include/czk.h: tools/polyvm_host.hpp; no torch, no Python)\", \"workload\": \"%s\", \"constraints\": %zu, "
            "\"parties\": %zu, \"layout\": \"%s\", \"transport\": \"%s\", \"share_lanes\": %zu, \"steps\": %zu, \"warmup\": %zu, \"proofs_in_flight\": %zu, \"ms_per_proof\": %.4f, \"proofs_per_s\": %.5f, "
            "\"latency_ms_single_proof\": %.3f, \"first_proof_ms\": %.3f, \"setup_s\": %.3f, \"msms_per_proof\": %.1f, \"ntt_lanes_per_proof\": %.1f, "
-           "\"arena_peak_gb\": %.2f, \"commit_opens\": %s, \"in_flight_provers_equal\": true, \"output_sha256\": \"%s\"%s%s}\n",
+           "\"arena_peak_gb\": %.2f, \"commit_opens\": %s, \"commit_hash\": %s, \"in_flight_provers_equal\": true, \"output_sha256\": \"%s\"%s%s}\n",
            workload, workload, n, parties, party ? "party (one process per party, evaluations opened through czk_net)" : "one process",
            party ? transport_name(transport) : "none", lanes, steps, warmup,
            inflight, dt / steps * 1e3, steps / dt, alone_ms, first_ms, setup_s, (double)msms / steps,
-           (double)ntts / steps, provers[0].B->arena_peak_bytes() / 1e9, (party && !plonk) ? (commit_opens ? "true" : "false") : "null", hex(digest, 32).c_str(), breakdown ? ", \"single_proof_breakdown\": " : "", breakdown_json.c_str());
+           (double)ntts / steps, provers[0].B->arena_peak_bytes() / 1e9, (party && !plonk) ? (commit_opens ? "true" : "false") : "null",
+           (party && !plonk && commit_opens) ? (tree_commit_opens ? "\"tree\"" : "\"sha256\"") : "null", hex(digest, 32).c_str(), breakdown ? ", \"single_proof_breakdown\": " : "", breakdown_json.c_str());
     if (net) {
         provers[0].B->net = nullptr;
         net.reset();   // the communicator goes before its context

@@ -198,6 +198,7 @@ class Machine {
     // ONE batch_open -- GszFieldShare::batch_open (lanes = 1) or SpdzFieldShare::batch_open (lanes = 2: sh, mac) -- on values that stay in HBM
     const czk::Net* net = nullptr;
     bool net_gsz = false;
+    bool tree_commit_opens = false;            // ... with the tree commitment hashed on the GPU (CZK_OPEN_COMMIT_TREE) instead of SHA-256 over a download
     bool commit_opens = true;                  // SPDZ: dx_ts through Net::atomic_broadcast, as the reference does (share/spdz.rs:179, channel.rs:50-75)
     unsigned gsz_degree = 0;
     Fr mac_share{};
@@ -656,7 +657,7 @@ class Machine {
             if (net_gsz) net->gsz_batch_open(sh.p(), k, gsz_degree, res.p());
             else {
                 uint64_t bad = 0;
-                net->check(czk_spdz_batch_open(net->raw(), sh.p(), mac.p(), mac_share.l, k, res.p(), commit_opens ? CZK_OPEN_COMMIT : 0, &bad));
+                net->check(czk_spdz_batch_open(net->raw(), sh.p(), mac.p(), mac_share.l, k, res.p(), !commit_opens ? 0 : tree_commit_opens ? CZK_OPEN_COMMIT | CZK_OPEN_COMMIT_TREE : CZK_OPEN_COMMIT, &bad));
                 if (bad) throw czk::Panic(CZK_ERR_CHECK, "assertion failed: sum.is_zero() (SPDZ MAC check, share/spdz.rs:183)");
             }
             const size_t kk[3] = {1, 1, k};
