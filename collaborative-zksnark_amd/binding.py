@@ -34,6 +34,17 @@ CZK_ERR_NET, CZK_ERR_CHECK = 5, 6
 _STATUS = {1: "CZK_ERR_SIZE", 2: "CZK_ERR_HIP", 3: "CZK_ERR_ARG", 4: "CZK_ERR_NOMEM", 5: "CZK_ERR_NET", 6: "CZK_ERR_CHECK"}
 
 
+CZK_SHARE_OP_MUL, CZK_SHARE_OP_INV, CZK_SHARE_OP_PARTIAL_PRODUCTS = 0, 1, 2   # czk_share_material_counts
+
+
+def _share_material_counts(L, op: int, n: int):
+    t, p = C.c_size_t(0), C.c_size_t(0)
+    rc = L.czk_share_material_counts(C.c_int(op), C.c_size_t(n), C.byref(t), C.byref(p))
+    if rc:
+        raise CzkError(rc, "czk_share_material_counts: unknown op or a count that overflows")
+    return t.value, p.value
+
+
 def open_commit_flags(commit) -> int:
     """commit = True | False | "tree" -> the flags of czk_spdz_batch_open"""
     if isinstance(commit, str):
@@ -498,6 +509,32 @@ class Context:
         """dx_t = mac_share * value - mac on device vectors (share/spdz.rs:176-180); mac_share: (4,) uint64 Montgomery."""
         ms = np.ascontiguousarray(mac_share, np.uint64).reshape(4)
         self._ck(self._L.czk_fr_spdz_dx(self._h, _ptr(value_ptr), _ptr(mac_ptr), _ptr(ms), _ptr(out_ptr), C.c_size_t(n)))
+
+    # ---- FieldShare::batch_mul / batch_inv / partial_products on device lanes (czk.h; csrc/share_mul.hip) ---------------------
+    def share_material_counts(self, op: int, n: int):
+        """(triples, inverse pairs) one call of `op` (CZK_SHARE_OP_*) over n elements consumes"""
+        return _share_material_counts(self._L, op, n)
+
+    def _share_call(self, fn, lpp, parties, mac_shares, ptrs, out_ptr, n):
+        ms = None if mac_shares is None else np.ascontiguousarray(mac_shares, np.uint64).reshape(-1, 4)
+        assert ms is None or ms.shape[0] >= parties
+        bad, zero = C.c_uint64(0), C.c_uint64(0)
+        self._ck(fn(self._h, C.c_size_t(lpp), C.c_size_t(parties), _ptr(ms), *[_ptr(p) for p in ptrs], _ptr(out_ptr), C.c_size_t(n), C.byref(bad),
+                    C.byref(zero)))
+        return bad.value, zero.value
+
+    def share_batch_mul(self, lpp: int, parties: int, mac_shares, x_ptr, y_ptr, tx_ptr, ty_ptr, tz_ptr, out_ptr, n: int):
+        """czk_share_batch_mul: every vector lpp * parties device lanes; mac_shares (parties, 4) Montgomery limbs (None for lpp = 1).
+        Returns (failed MAC checks, 0)."""
+        return self._share_call(self._L.czk_share_batch_mul, lpp, parties, mac_shares, (x_ptr, y_ptr, tx_ptr, ty_ptr, tz_ptr), out_ptr, n)
+
+    def share_batch_inv(self, lpp: int, parties: int, mac_shares, x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr, out_ptr, n: int):
+        """czk_share_batch_inv -> (failed MAC checks, zero divisors)"""
+        return self._share_call(self._L.czk_share_batch_inv, lpp, parties, mac_shares, (x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr), out_ptr, n)
+
+    def share_partial_products(self, lpp: int, parties: int, mac_shares, x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr, out_ptr, n: int):
+        """czk_share_partial_products -> (failed MAC checks, zero divisors)"""
+        return self._share_call(self._L.czk_share_partial_products, lpp, parties, mac_shares, (x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr), out_ptr, n)
 
     def share_domain_constants(self, parties: int):
         out = np.zeros((3, 4), dtype=np.uint64)
@@ -1048,6 +1085,26 @@ class Net:
 
     def add_batch_open(self, val_ptr, n: int, out_ptr):
         self._ck(self._L.czk_add_batch_open(self._h, _ptr(val_ptr), C.c_size_t(n), _ptr(out_ptr)))
+
+    # ---- the shared-value protocols, this party's lpp lanes (czk_net_share_*); commit as in spdz_batch_open ------------------------
+    def share_material_counts(self, op: int, n: int):
+        return _share_material_counts(self._L, op, n)
+
+    def _share_call(self, fn, lpp, mac_share, ptrs, out_ptr, n, commit):
+        ms = None if mac_share is None else np.ascontiguousarray(mac_share, np.uint64).reshape(4)
+        bad, zero = C.c_uint64(0), C.c_uint64(0)
+        self._ck(fn(self._h, C.c_size_t(lpp), _ptr(ms), *[_ptr(p) for p in ptrs], _ptr(out_ptr), C.c_size_t(n), C.c_int(open_commit_flags(commit)),
+                    C.byref(bad), C.byref(zero)))
+        return bad.value, zero.value
+
+    def share_batch_mul(self, lpp: int, mac_share, x_ptr, y_ptr, tx_ptr, ty_ptr, tz_ptr, out_ptr, n: int, commit: bool | str = True):
+        return self._share_call(self._L.czk_net_share_batch_mul, lpp, mac_share, (x_ptr, y_ptr, tx_ptr, ty_ptr, tz_ptr), out_ptr, n, commit)
+
+    def share_batch_inv(self, lpp: int, mac_share, x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr, out_ptr, n: int, commit: bool | str = True):
+        return self._share_call(self._L.czk_net_share_batch_inv, lpp, mac_share, (x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr), out_ptr, n, commit)
+
+    def share_partial_products(self, lpp: int, mac_share, x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr, out_ptr, n: int, commit: bool | str = True):
+        return self._share_call(self._L.czk_net_share_partial_products, lpp, mac_share, (x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr), out_ptr, n, commit)
 
     def gsz_batch_open(self, val_ptr, n: int, out_ptr, degree: int = 0, degrees_ptr=None) -> int:
         bad = C.c_uint64(0)

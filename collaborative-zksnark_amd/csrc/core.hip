@@ -399,6 +399,7 @@ extern "C" void czk_ctx_destroy(czk_ctx* ctx) {
     if (ctx->ntt_scratch.p) (void)hipFree(ctx->ntt_scratch.p);
     if (ctx->poly_scratch.p) (void)hipFree(ctx->poly_scratch.p);
     if (ctx->open_bad) (void)hipFree(ctx->open_bad);
+    if (ctx->share_cnt) (void)hipFree(ctx->share_cnt);
     for (auto& b : ctx->stage_pool) (void)hipFree(b.p);
     ctx->stage_pool.clear();
     if (ctx->share_tab.p) (void)hipFree(ctx->share_tab.p);

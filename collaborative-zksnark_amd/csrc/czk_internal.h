@@ -161,6 +161,7 @@ struct czk_ctx {
     bool msm_no_te = false;          // lab "msm_no_te": G1 keys registered from now on keep the XYZZ kernels (what CZK_MEM_ANY_POINTS does per key)
     long net_create_timeout_ms = 0;  // "net_create_timeout_ms": how long czk_net_create on this context waits for its peers (0 = the communicator's default, 120 s)
     unsigned long long* open_bad = nullptr;   // device counter of czk_fr_spdz_open (allocated once)
+    unsigned long long* share_cnt = nullptr;  // device counters of the shared-value protocols (share_mul.hip): [0] failed MAC checks, [1] zero divisors
     // lab "chaos": schedule perturbation (tests/test_chaos.py).  Non-zero = seed: every stage boundary (the profiling brackets around the sort / accumulate /
     // reduce / NTT / polynomial stages, the result copy) first enqueues a spin kernel of random length on the stage's stream and / or sleeps on the host, and the
     // MSM workspace ring hands out its slots in random order.  Results must not change: every ordering the library relies on has to be an event wait or stream
@@ -271,6 +272,22 @@ int ensure_buf(czk_ctx* ctx, DeviceBuf& b, size_t bytes);
 // that uses it has been ENQUEUED on ctx->stream -- every later user enqueues on the same stream, so re-use is ordered
 int stage_take(czk_ctx* ctx, size_t bytes, DeviceBuf* out);
 void stage_give(czk_ctx* ctx, const DeviceBuf& b);
+// one staging buffer as a call's workspace, given back on every return path
+struct StageHold {
+    czk_ctx* ctx;
+    DeviceBuf b{};
+    bool held = false;
+    explicit StageHold(czk_ctx* c) : ctx(c) {}
+    StageHold(const StageHold&) = delete;
+    int take(size_t bytes) {
+        int rc = stage_take(ctx, bytes, &b);
+        held = rc == 0;
+        return rc;
+    }
+    ~StageHold() {
+        if (held) stage_give(ctx, b);
+    }
+};
 int get_domain(czk_ctx* ctx, unsigned log_d, DomainTables** out);
 
 // lab build, option "chaos": a random delay on `st` and / or on the calling thread (no-op otherwise, and in the product build)
@@ -333,6 +350,22 @@ int upload_pageable(czk_ctx* ctx, void* dev, const void* host, size_t bytes);
 int download_pageable(czk_ctx* ctx, void* host, const void* dev, size_t bytes);
 // implemented in commit_tree.hip: the tree commitments (czk.h "czk tree commitment v1") of `lanes` DEVICE vectors; rand32 / out32: lanes x 32 bytes, host.  Blocking.
 int commit_tree_device(czk_ctx* ctx, const u64* a, size_t lanes, size_t n, size_t stride, const uint8_t* rand32, uint8_t* out32);
+// implemented in share_mul.hip: the kernels of the shared-value protocols that the one-party-per-communicator forms (net.hip) launch between their opens.
+// A ShareVec is `lanes` vectors `lane_stride` elements apart; elem_stride 0 repeats each lane's first element (partial_products' `vec![m[0]; n]`).
+struct ShareVec {
+    const u64* p;
+    size_t lane_stride;
+    unsigned elem_stride;
+};
+int share_counters(czk_ctx* ctx);   // allocates (once) and zeroes ctx->share_cnt on the context's stream
+int share_counters_read(czk_ctx* ctx, uint64_t* out_bad, uint64_t* out_zero);   // blocking read-back of the two counters (either pointer may be null)
+// open[l][0, n) = x_l + tx_l and open[l][n, 2n) = y_l + ty_l for a party's `lanes` lanes (open: lanes x 2n, dense): the one open of a batch_mul
+int share_mask_launch(czk_ctx* ctx, unsigned lanes, ShareVec x, ShareVec y, ShareVec tx, ShareVec ty, u64* open, size_t n);
+// out_l = tz_l - ty_l sx - tx_l oy + shift(sx oy) for a party's lpp lanes (sx = opened[0, n), oy = opened[n, 2n)): sh lane shifts on the king, mac lane by mac_share
+int share_combine_launch(czk_ctx* ctx, unsigned lpp, bool king, const Fr& mac_share, const u64* opened, ShareVec tx, ShareVec ty, ShareVec tz, u64* out,
+                         size_t out_stride, size_t n);
+// out_l[i] = c_l[i] * (k[i] * prefix[i]) (prefix null: c_l[i] * k[i]); k[i] == 0 (czk_fr_batch_inverse kept a zero) adds one to ctx->share_cnt[1]
+int share_scale_launch(czk_ctx* ctx, unsigned lanes, ShareVec c, const u64* k, const u64* prefix, u64* out, size_t out_stride, size_t n);
 // implemented in ntt.hip
 // `addend` (lanes x D canonical Fr, not the lanes being transformed) rides on the last pass's store: a coset inverse transform writes
 // (coset_ifft(data) - addend) * *scale, a forward or coset forward transform writes its output + addend (scale unused).  Same values as the pointwise kernels.

@@ -1,5 +1,5 @@
 // net.hip -- czk_net_*: the transport of the MPC opens behind the C ABI, and the reference's batch opens
-// as single calls on device lanes.  Host code only (the kernels it launches live in share.hip / ntt.hip).
+// as single calls on device lanes.  Host code only (the kernels it launches live in share.hip / share_mul.hip / ntt.hip).
 //
 //   reference                                                            here
 //   MpcMultiNet::broadcast          mpc-net/src/multi.rs:145-173          czk_net_broadcast       (RCCL: ncclAllGather | grouped ncclSend / ncclRecv)
@@ -10,6 +10,7 @@
 //   AdditiveFieldShare::batch_open  mpc-algebra/src/share/add.rs:256-259  czk_add_batch_open
 //   GszFieldShare::batch_open       share/gsz20/mod.rs:286-300, 440-466   czk_gsz_batch_open
 //   gsz20::batch_king_compute       share/gsz20/mod.rs:494-527            czk_gsz_batch_king_compute
+//   FieldShare::batch_mul / batch_inv / partial_products  share/field.rs:97-182   czk_net_share_batch_mul / _batch_inv / _partial_products
 //   Vec<Fr> wire format             algebra/serialize/src/lib.rs:220-229  czk_fr_vec_serialize / _deserialize
 //
 // Two transports (include/czk.h): RCCL for one party per GPU -- every exchange is enqueued on the context's stream, so the kernels that
@@ -873,4 +874,116 @@ extern "C" int czk_gsz_batch_king_compute(czk_net* n, const uint64_t* val, size_
             NET_HIP(n, hipMemcpyAsync(ans + 4 * cnt * p, ans, cnt * 32, hipMemcpyDeviceToDevice, n->ctx->stream));
     }
     return czk_net_recv_from_king(n, ans, cnt * 32, out, CZK_MEM_DEVICE);
+}
+
+// ---- FieldShare::batch_mul / batch_inv / partial_products for one party per communicator (share/field.rs:97-182; kernels in share_mul.hip) -----------------
+// Every round is the reference's, in its order, except that the two independent opens of a batch_mul go out as ONE open of 2 cnt elements.
+namespace {
+struct NetShare {
+    czk_net* n;
+    size_t lpp;
+    const uint64_t* mac_share;   // host; SPDZ only
+    Fr ms;
+    int flags;
+    uint64_t bad = 0;
+};
+int net_share_args(czk_net* n, const char* what, size_t lpp, const uint64_t* mac_share, bool null_vec, size_t cnt, int flags, uint64_t* out_bad, uint64_t* out_zero,
+                   NetShare* s, bool* work) {
+    *work = false;
+    if (!n) return CZK_ERR_ARG;
+    if (!n->ctx) return net_err(n, CZK_ERR_ARG, std::string(what) + " needs a communicator created with a context");
+    if (!out_bad || !out_zero) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null count output");
+    *out_bad = *out_zero = 0;
+    if (lpp != 1 && lpp != 2) return net_err(n, CZK_ERR_ARG, std::string(what) + ": lpp is 1 (additive) or 2 (SPDZ)");
+    if (!cnt) return CZK_OK;
+    if (null_vec || (lpp == 2 && !mac_share)) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null argument");
+    if (cnt > ((size_t)1 << 54)) return net_err(n, CZK_ERR_SIZE, std::string(what) + ": the lane arrays' byte count overflows");
+    NET_HIP(n, hipSetDevice(n->ctx->device));
+    s->n = n, s->lpp = lpp, s->mac_share = mac_share, s->flags = flags;
+    s->ms = lpp == 2 ? host_fr(mac_share) : Fr::zero();
+    *work = true;
+    return CZK_OK;
+}
+// the scheme's batch_open of this party's lanes (cnt apart); failed MAC checks add up in s.bad
+int net_share_open(NetShare& s, const u64* lanes, size_t cnt, u64* out_value) {
+    if (s.lpp == 1) return czk_add_batch_open(s.n, lanes, cnt, out_value);
+    uint64_t b = 0;
+    CZK_TRY(czk_spdz_batch_open(s.n, lanes, lanes + 4 * cnt, s.mac_share, cnt, out_value, s.flags, &b));
+    s.bad += b;
+    return CZK_OK;
+}
+size_t net_share_mul_ws(size_t lpp, size_t cnt) { return (lpp + 1) * 2 * cnt * 32; }
+// ws: lpp x 2 cnt masked factors, then the 2 cnt opened values
+int net_share_mul(NetShare& s, ShareVec x, ShareVec y, const u64* tx, const u64* ty, const u64* tz, size_t T, size_t first, u64* ws, u64* out, size_t cnt) {
+    czk_net* n = s.n;
+    u64* opened = ws + 4 * s.lpp * 2 * cnt;
+    const ShareVec vx{tx + 4 * first, T, 1}, vy{ty + 4 * first, T, 1}, vz{tz + 4 * first, T, 1};
+    NET_CTX(n, share_mask_launch(n->ctx, (unsigned)s.lpp, x, y, vx, vy, ws, cnt));
+    CZK_TRY(net_share_open(s, ws, 2 * cnt, opened));
+    NET_CTX(n, share_combine_launch(n->ctx, (unsigned)s.lpp, n->rank == 0, s.ms, opened, vx, vy, vz, out, cnt, cnt));
+    return CZK_OK;
+}
+}  // namespace
+
+extern "C" int czk_net_share_batch_mul(czk_net* n, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* y, const uint64_t* tx,
+                                       const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t cnt, int flags, uint64_t* out_bad, uint64_t* out_zero) {
+    NetShare s;
+    bool work;
+    CZK_TRY(net_share_args(n, "czk_net_share_batch_mul", lpp, mac_share, !x || !y || !tx || !ty || !tz || !out, cnt, flags, out_bad, out_zero, &s, &work));
+    if (!work) return CZK_OK;
+    StageHold ws(n->ctx);
+    NET_CTX(n, ws.take(net_share_mul_ws(lpp, cnt)));
+    CZK_TRY(net_share_mul(s, ShareVec{x, cnt, 1}, ShareVec{y, cnt, 1}, tx, ty, tz, cnt, 0, (u64*)ws.b.p, out, cnt));
+    NET_HIP(n, hipStreamSynchronize(n->ctx->stream));   // like the opens: the call's outputs are complete when it returns
+    *out_bad = s.bad;
+    return CZK_OK;
+}
+
+extern "C" int czk_net_share_batch_inv(czk_net* n, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
+                                       const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t cnt, int flags, uint64_t* out_bad,
+                                       uint64_t* out_zero) {
+    NetShare s;
+    bool work;
+    CZK_TRY(net_share_args(n, "czk_net_share_batch_inv", lpp, mac_share, !x || !pb || !pc || !tx || !ty || !tz || !out, cnt, flags, out_bad, out_zero, &s, &work));
+    if (!work) return CZK_OK;
+    StageHold ws(n->ctx);
+    NET_CTX(n, ws.take(net_share_mul_ws(lpp, cnt) + (lpp + 2) * cnt * 32));
+    u64 *mulws = (u64*)ws.b.p, *prod = mulws + net_share_mul_ws(lpp, cnt) / 8, *v = prod + 4 * lpp * cnt, *vinv = v + 4 * cnt;
+    CZK_TRY(net_share_mul(s, ShareVec{x, cnt, 1}, ShareVec{pb, cnt, 1}, tx, ty, tz, cnt, 0, mulws, prod, cnt));
+    CZK_TRY(net_share_open(s, prod, cnt, v));
+    NET_CTX(n, czk_fr_batch_inverse(n->ctx, v, cnt, nullptr, vinv, CZK_MEM_DEVICE));
+    NET_CTX(n, share_counters(n->ctx));
+    NET_CTX(n, share_scale_launch(n->ctx, (unsigned)lpp, ShareVec{pc, cnt, 1}, vinv, nullptr, out, cnt, cnt));
+    NET_CTX(n, share_counters_read(n->ctx, nullptr, out_zero));
+    *out_bad = s.bad;
+    return CZK_OK;
+}
+
+extern "C" int czk_net_share_partial_products(czk_net* n, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
+                                              const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t cnt, int flags, uint64_t* out_bad,
+                                              uint64_t* out_zero) {
+    NetShare s;
+    bool work;
+    CZK_TRY(net_share_args(n, "czk_net_share_partial_products", lpp, mac_share, !x || !pb || !pc || !tx || !ty || !tz || !out, cnt, flags, out_bad, out_zero, &s,
+                           &work));
+    if (!work) return CZK_OK;
+    const size_t T = 4 * cnt, P = 2 * cnt + 1;
+    StageHold ws(n->ctx);
+    NET_CTX(n, ws.take(net_share_mul_ws(lpp, cnt) + (2 * lpp + 4) * cnt * 32));
+    u64 *mulws = (u64*)ws.b.p, *la = mulws + net_share_mul_ws(lpp, cnt) / 8, *lb = la + 4 * lpp * cnt, *mxm = lb + 4 * lpp * cnt, *run = mxm + 4 * cnt, *mms = run + 4 * cnt,
+        *inv = mms + 4 * cnt;
+    const ShareVec m_inv1{pc + 4, P, 1};                                                                     // m_inv[1..]
+    CZK_TRY(net_share_mul(s, ShareVec{pb, P, 1}, ShareVec{x, cnt, 1}, tx, ty, tz, T, 0, mulws, la, cnt));   // mx = m[..n] x
+    CZK_TRY(net_share_mul(s, ShareVec{la, cnt, 1}, m_inv1, tx, ty, tz, T, cnt, mulws, lb, cnt));            // mxm = mx m_inv[1..]
+    CZK_TRY(net_share_open(s, lb, cnt, mxm));
+    NET_CTX(n, czk_fr_prefix_product(n->ctx, mxm, cnt, run, CZK_MEM_DEVICE));                               // the local loop :169-172
+    CZK_TRY(net_share_mul(s, ShareVec{pb, P, 0}, m_inv1, tx, ty, tz, T, 2 * cnt, mulws, la, cnt));          // mms = m_0 m_inv[1..]
+    CZK_TRY(net_share_mul(s, ShareVec{la, cnt, 1}, ShareVec{pb + 4 * (cnt + 1), P, 1}, tx, ty, tz, T, 3 * cnt, mulws, lb, cnt));   // batch_inv(mms)
+    CZK_TRY(net_share_open(s, lb, cnt, mms));
+    NET_CTX(n, czk_fr_batch_inverse(n->ctx, mms, cnt, nullptr, inv, CZK_MEM_DEVICE));
+    NET_CTX(n, share_counters(n->ctx));
+    NET_CTX(n, share_scale_launch(n->ctx, (unsigned)lpp, ShareVec{pc + 4 * (cnt + 1), P, 1}, inv, run, out, cnt, cnt));
+    NET_CTX(n, share_counters_read(n->ctx, nullptr, out_zero));
+    *out_bad = s.bad;
+    return CZK_OK;
 }

@@ -157,26 +157,44 @@ def _as_mont(vals) -> np.ndarray:
 
 def prover_inputs(B, idx: dict, instance, witness, mask=None, seed: int = 0x3A26) -> dict:
     """The assignment side of marlin_prove's inputs for an index made by `index`, merged with it: instance = the formatted input [1, ...], witness = the
-    witness variables, both as integers or as (n, 4) Montgomery limbs.  "x" / "x_ints": the input padded with zeros to X; "w": the full assignment on H
+    witness variables, both as integers or as (n, 4) Montgomery limbs; the witness may also be a (lanes, n, 4) device array of share lanes (B.lanes of
+    them), as plonk.prover_inputs takes the assignment.  "x" / "x_ints": the input padded with zeros to X; "w": the full assignment on H
     at the re-indexed positions (dummy variables = 1, unused positions 0: prover.rs:334-351) on every lane; "z_a", "z_b": czk_r1cs_matvec of the BALANCED
     A and B over the share lanes; "mask_poly": 3 |H| coefficients -- `mask` as (1, 3 |H|, 4) backend array, or B.random(seed, 3 |H|) -- with coefficient 0
     lowered so that the remainder modulo v_H has constant term 0 (prover.rs:373-376)."""
     info, H, X = idx["info"], idx["H"], idx["X"]
     nv = info["num_variables"]
-    x, w = _as_mont(instance), _as_mont(witness)
-    if x.shape[0] > X or X + w.shape[0] > nv:
+    shared = hasattr(witness, "data_ptr")
+    x = _as_mont(instance)
+    if shared:
+        if witness.dim() != 3 or witness.shape[0] != B.lanes or witness.shape[2] != 4:
+            raise ValueError(f"share lanes must be ({B.lanes}, n, 4)")
+        n_w = int(witness.shape[1])
+    else:
+        w = _as_mont(witness)
+        n_w = w.shape[0]
+    if x.shape[0] > X or X + n_w > nv:
         raise ValueError("assignment longer than the index's variables")
     full = np.zeros((nv, 4), dtype=np.uint64)
     full[:x.shape[0]] = x
-    full[X:X + w.shape[0]] = w
-    full[X + w.shape[0]:] = _ONE                                               # make_matrices_square's dummy variables
-    on_h = np.zeros((H, 4), dtype=np.uint64)
-    on_h[reindex(H, X, np.arange(nv))] = full
+    if not shared:
+        full[X:X + n_w] = w
+    full[X + n_w:] = _ONE                                                      # make_matrices_square's dummy variables
     inp = dict(idx)
     inp["x"] = B.upload(full[:X])
     inp["x_ints"] = [unmont(v) for v in full[:X]]
-    inp["w"] = polyvm.shared_copy(B, B.upload(on_h))
-    z = polyvm.shared_copy(B, B.upload(full))
+    if shared:
+        # the public entries (input, dummy variables) as from_public on the lifting lanes, the witness on its share lanes; placed on H by index
+        z = B.lifted(B.upload(full))
+        z[:, X:X + n_w] = witness
+        at_h = B.torch.from_numpy(reindex(H, X, np.arange(nv)).astype(np.int64)).to(z.device)
+        inp["w"] = B.zeros(B.lanes, H)
+        inp["w"][:, at_h] = z
+    else:
+        on_h = np.zeros((H, 4), dtype=np.uint64)
+        on_h[reindex(H, X, np.arange(nv))] = full
+        inp["w"] = polyvm.shared_copy(B, B.upload(on_h))
+        z = polyvm.shared_copy(B, B.upload(full))
     for key, m in (("z_a", "a"), ("z_b", "b")):
         rp, col, cf = idx["matrices"][m]
         mat = B.ctx.r1cs_matrix_register(rp, col, cf, nv)

@@ -502,3 +502,40 @@ def combine_split_results(ctx, czk, per_proof: list, keys=("h", "l", "a", "b_g1"
             at += lanes * jw
         out.append(comb)
     return out
+
+
+# ---- FieldShare::batch_mul / batch_inv / partial_products with one process per party (czk_net_share_*, include/czk.h) ------------------------------------
+# Only over a czk_net communicator (use_net): the protocols are single C-ABI calls there, and no torch.distributed restatement is kept beside them.
+def _share_net_call(ctx, name: str, lpp: int, mac_share, vecs, n: int, commit):
+    if _NET is None:
+        raise RuntimeError(f"parallel.{name} runs over a czk_net communicator: call parallel.use_net(parallel.make_net(ctx, 'shm')) first")
+    vecs = [v.contiguous() for v in vecs]
+    if any(not v.is_cuda or v.dim() != 3 or v.shape[0] != lpp or v.shape[2] != 4 for v in vecs):
+        raise ValueError(f"parallel.{name}: every vector is this party's ({lpp}, k, 4) device lanes")
+    out = torch.empty((lpp, n, 4), dtype=vecs[0].dtype, device=vecs[0].device)
+    for v in vecs:
+        _net_in(ctx, v)
+    try:
+        bad, zero = getattr(_NET, name)(lpp, mac_share, *[v.data_ptr() for v in vecs], out.data_ptr(), n, commit=commit)
+    except Exception as e:
+        if getattr(e, "code", None) == 6:
+            raise MpcCheckError(str(e)) from e
+        raise
+    if bad or zero:
+        raise MpcCheckError(f"{name} of {n} shared elements: {bad} failed MAC check(s), {zero} zero divisor(s)")
+    return _after_consume(ctx, out)
+
+
+def share_batch_mul(ctx, lpp: int, mac_share, x, y, tx, ty, tz, commit: bool | str = True) -> torch.Tensor:
+    """this party's lanes of x * y (share/field.rs:97-127) from its lanes of x, y and of a triple; mac_share: (4,) uint64, None for additive shares"""
+    return _share_net_call(ctx, "share_batch_mul", lpp, mac_share, (x, y, tx, ty, tz), x.shape[1], commit)
+
+
+def share_batch_inv(ctx, lpp: int, mac_share, x, pb, pc, tx, ty, tz, commit: bool | str = True) -> torch.Tensor:
+    """this party's lanes of 1 / x (share/field.rs:135-148); material as czk_share_material_counts(CZK_SHARE_OP_INV) says"""
+    return _share_net_call(ctx, "share_batch_inv", lpp, mac_share, (x, pb, pc, tx, ty, tz), x.shape[1], commit)
+
+
+def share_partial_products(ctx, lpp: int, mac_share, x, pb, pc, tx, ty, tz, commit: bool | str = True) -> torch.Tensor:
+    """this party's lanes of the running products x_0 ... x_i (share/field.rs:163-182)"""
+    return _share_net_call(ctx, "share_partial_products", lpp, mac_share, (x, pb, pc, tx, ty, tz), x.shape[1], commit)

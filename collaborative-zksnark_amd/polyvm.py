@@ -10,9 +10,13 @@ What is restated: the call sequence and sizes of
     mpc-plonk/src/lib.rs:110-258 (prove_unit_product, prove_wiring), :259-340 (prove_public, prove_gates), :343-448 (eval, commit,
     prove);  marlin/src/ahp/prover.rs:300-704 (three AHP rounds), marlin/src/lib.rs:176-318 (commitments and openings)
 What is NOT: protocol logic.  Fiat-Shamir challenges are fixed field elements (the hashing of commitments is host-side glue),
-blinding factors are fixed, and a product of two shared vectors is the lane-wise product (for the reference's king_share
-stand-in sharing every party holds the value itself, mpc-algebra/src/share/gsz20/mod.rs:190-213; the degree-reduction exchange
-of `mult` is an open, covered by parallel.gsz_batch_open).
+and blinding factors are fixed.  Products of shared vectors: by default (`sharing=None`) a product of two shared vectors is the lane-wise
+product, right for the reference's king_share stand-in sharing alone, where every party holds the value itself
+(mpc-algebra/src/share/gsz20/mod.rs:190-213; the degree-reduction exchange of `mult` is an open, covered by parallel.gsz_batch_open).  With
+`GpuBackend(..., sharing=Sharing(lpp, parties, source))` the lanes are a real additive or SPDZ sharing and `mul`, `inverse` and
+`prefix_product` of shared arrays are FieldShare::batch_mul / batch_inv / partial_products (czk_share_*, include/czk.h) on correlated randomness
+from `source`; `open_shared_proof` is the parties' last step.  The `lift` tuple keeps its 0 / 1 meaning, so under `sharing` the MAC key is the
+reference's 0 / 1 key (the king's share is one, share/spdz.rs:30-37); the C calls take any key.
 """
 from __future__ import annotations
 
@@ -234,6 +238,95 @@ class Backend:
         return None
 
 
+class SharingError(RuntimeError):
+    """a MAC check failed, or a shared value that had to be inverted opened to zero (the reference asserts / unwraps there)"""
+
+
+class Sharing:
+    """The lanes of a GpuBackend as a real sharing: lpp = 1 additive, lpp = 2 SPDZ (lane lpp p = party p's sh, lane lpp p + 1 its mac), `parties`
+    parties, correlated randomness from `source` (DummySource, SeededDealer).  MAC key: the reference's 0 / 1 key (see the module's head)."""
+
+    def __init__(self, lpp: int, parties: int, source, rank: int | None = None):
+        """rank=None: all parties' lanes on one backend (lpp * parties lanes).  rank=r: one process per party -- the backend holds party r's lpp
+        lanes and the protocols run over the czk_net communicator given to parallel.use_net (the CZK_NET_SHM transport is the tested one); every
+        party's source must deal the same material (the same seed), of which it keeps its own lanes."""
+        if lpp not in (1, 2) or not 1 <= parties <= 32 or (rank is not None and not 0 <= rank < parties):
+            raise ValueError("Sharing: lpp is 1 (additive) or 2 (SPDZ), 1 to 32 parties, rank below parties")
+        if rank is not None and lpp == 1:
+            # a backend tells shared from public arrays by their lane count, and one party's additive share is one lane, like public data
+            raise ValueError("Sharing(rank=...) needs SPDZ shares (lpp = 2): a single additive lane cannot be told from a public array")
+        self.lpp, self.parties, self.lanes, self.source, self.rank = lpp, parties, lpp * parties, source, rank
+        self.lift = tuple([1] * lpp + [0] * (lpp * (parties - 1)))                 # the king's lanes take public addends
+        self.mac_shares = np.stack([mont(1 if p == 0 else 0) for p in range(parties)])
+        self.backend_lanes = self.lanes
+        if rank is not None:
+            self.backend_lanes, self.lift = lpp, tuple([1 if rank == 0 else 0] * lpp)
+
+    def own(self, full):
+        """this backend's lanes of a (lpp * parties, n, 4) array dealt for all parties"""
+        return full if self.rank is None else full[self.lpp * self.rank:self.lpp * (self.rank + 1)].contiguous()
+
+
+class DummySource:
+    """DummyFieldTripleSource (mpc-algebra/src/wire/field.rs:41-76): every triple and every inverse pair is one on the king's lanes, zero elsewhere."""
+
+    def __init__(self):
+        self._ones = {}      # (backend, n) -> the array: the material is constant, so it is made once per length
+
+    def _one(self, B, n):
+        if (id(B), n) not in self._ones:
+            self._ones[(id(B), n)] = B.lifted(B.const(1, n))
+        return self._ones[(id(B), n)]
+
+    def triples(self, B, n: int):
+        one = self._one(B, n)
+        return one, one, one
+
+    def inv_pairs(self, B, n: int, inverses: int = 0):
+        one = self._one(B, n)
+        return one, one
+
+
+class SeededDealer:
+    """Random triples and inverse pairs from a seed, made on the device from B.random, fr_vec_op, fr_batch_inverse and a random split across the
+    parties.  INSECURE BY CONSTRUCTION: this one process knows every value it deals.  For tests and measurements only -- a deployment gets its
+    correlated randomness from a preprocessing phase, which is outside this project."""
+
+    def __init__(self, seed: int):
+        self.seed, self.drawn = int(seed), 0
+
+    def _random(self, B, n):
+        self.drawn += 1
+        return B.random((self.seed * 1000003 + self.drawn) & 0x7FFFFFFFFFFFFFFF, n)
+
+    def _split(self, B, v):
+        """public (1, n, 4) -> a random sharing: per kind of lane (sh; mac, which shares the same value under the 0 / 1 key) the parties but the
+        king get random elements and the king the rest"""
+        S, n = B.sharing, B.length(v)
+        kinds = []
+        for _ in range(S.lpp):
+            rest, parts = v, []
+            for _ in range(S.parties - 1):
+                r = self._random(B, n)
+                rest = B.sub(rest, r)
+                parts.append(r)
+            kinds.append([rest] + parts)
+        return S.own(B.lane_stack([kinds[k][p] for p in range(S.parties) for k in range(S.lpp)]))
+
+    def triples(self, B, n: int):
+        x, y = self._random(B, n), self._random(B, n)
+        return self._split(B, x), self._split(B, y), self._split(B, B.mul(x, y))
+
+    def inv_pairs(self, B, n: int, inverses: int = 0):
+        """n pairs (b, c): the first `inverses` with c = 1 / b (partial_products' m, m_inv), the rest with c = b (batch_inv's masks: c / open(x b)
+        is 1 / x) -- include/czk.h says which slot needs which"""
+        b = self._random(B, n)
+        c = b
+        if inverses:
+            c = B.concat([B.resized(B.inverse(b), inverses), B.drop_first(b, inverses)]) if inverses < n else B.inverse(b)
+        return self._split(B, b), self._split(B, c)
+
+
 def shared_stream_context(czk, device: int = 0):
     """A context whose kernels run on torch's current stream: GpuBackend mixes torch tensor operations (copies, concatenation,
     zero fills) with library calls, so both must be ordered on ONE stream (torch's default stream has handle 0, which the C ABI
@@ -248,9 +341,17 @@ class GpuBackend(Backend):
     """The product path: device tensors, every operation one or a few C-ABI calls on the context's stream -- which must be
     torch's current stream (shared_stream_context)."""
 
-    def __init__(self, czk, ctx, lanes: int, max_degree: int, base_seed: int = 0xBA5E5 + 77, lift=None, share_srs=None):
+    def __init__(self, czk, ctx, lanes: int, max_degree: int, base_seed: int = 0xBA5E5 + 77, lift=None, share_srs=None, sharing=None):
+        """sharing=None: shared products are lane-wise (the module's head).  sharing=Sharing(...): the lanes are that sharing; `mul`, `inverse` and
+        `prefix_product` of arrays on more than one lane run the reference's protocols and raise SharingError on a failed MAC check or a zero
+        divisor; public (one-lane) operands behave as ever."""
         import torch
         self.czk, self.ctx, self.lanes, self.torch = czk, ctx, lanes, torch
+        self.sharing = sharing
+        if sharing is not None:
+            if lanes != sharing.backend_lanes or (lift is not None and tuple(lift) != sharing.lift):
+                raise ValueError(f"sharing of {sharing.backend_lanes} lanes with lift {sharing.lift} on a backend of {lanes} lanes, lift {lift}")
+            lift = sharing.lift
         self.lift = tuple([1] * lanes) if lift is None else tuple(lift)
         self.dev = torch.device("cuda")
         # powers_of_g = [tau^i] G for a FIXED, KNOWN tau (a real SRS hides tau; knowing it lets bench.py verify every opening on the
@@ -290,6 +391,7 @@ class GpuBackend(Backend):
         self.msm_points = 0
 
     M = 1   # CZK_MEM_DEVICE
+    commit_opens = True   # Sharing(rank=...): the flags of the protocols' opens -- True, False or "tree" (binding.open_commit_flags)
 
     def verifier_key(self):
         """(g, gamma_g, h, beta_h) of this backend's SRS -- KZG10's VerifierKey (poly-commit/src/kzg10/data_structures.rs:173-190) as affine
@@ -429,7 +531,44 @@ class GpuBackend(Backend):
         return self._vec(1, a, b)
 
     def mul(self, a, b):
+        if self.sharing is not None and a.shape[0] > 1 and b.shape[0] > 1:
+            return self._share_call("batch_mul", a, b)
         return self._vec(2, a, b)
+
+    def _share_call(self, what, a, b=None):
+        """FieldShare::batch_mul / batch_inv / partial_products of shared arrays: one C call on material drawn from the sharing's source"""
+        S, n = self.sharing, a.shape[1]
+        a = a.contiguous()
+        assert a.shape[0] == S.backend_lanes and (b is None or b.shape == a.shape), (what, a.shape, None if b is None else b.shape)
+        if not n:
+            return self._new(S.backend_lanes, n)
+        op = {"batch_mul": self.czk.binding.CZK_SHARE_OP_MUL, "batch_inv": self.czk.binding.CZK_SHARE_OP_INV,
+              "partial_products": self.czk.binding.CZK_SHARE_OP_PARTIAL_PRODUCTS}[what]
+        n_triples, n_pairs = self.ctx.share_material_counts(op, n)
+        if n_pairs:
+            pb, pc = S.source.inv_pairs(self, n_pairs, inverses=n + 1 if what == "partial_products" else 0)
+        tx, ty, tz = S.source.triples(self, n_triples)
+        if S.rank is not None:                                                     # one process per party: the czk_net_share_* twins
+            from . import parallel
+            ms = S.mac_shares[S.rank] if S.lpp == 2 else None
+            try:
+                if what == "batch_mul":
+                    return parallel.share_batch_mul(self.ctx, S.lpp, ms, a, b.contiguous(), tx, ty, tz, commit=self.commit_opens)
+                fn = parallel.share_batch_inv if what == "batch_inv" else parallel.share_partial_products
+                return fn(self.ctx, S.lpp, ms, a, pb, pc, tx, ty, tz, commit=self.commit_opens)
+            except parallel.MpcCheckError as e:
+                raise SharingError(str(e)) from e
+        out = self._new(S.lanes, n)
+        if what == "batch_mul":
+            bad, zero = self.ctx.share_batch_mul(S.lpp, S.parties, S.mac_shares, a.data_ptr(), b.contiguous().data_ptr(), tx.data_ptr(), ty.data_ptr(),
+                                                 tz.data_ptr(), out.data_ptr(), n)
+        else:
+            fn = self.ctx.share_batch_inv if what == "batch_inv" else self.ctx.share_partial_products
+            bad, zero = fn(S.lpp, S.parties, S.mac_shares, a.data_ptr(), pb.data_ptr(), pc.data_ptr(), tx.data_ptr(), ty.data_ptr(), tz.data_ptr(),
+                           out.data_ptr(), n)
+        if bad or zero:
+            raise SharingError(f"{what} of {n} shared elements: {bad} failed MAC check(s), {zero} zero divisor(s)")
+        return out
 
     def scale(self, a, k):
         out = self._new(a.shape[0], a.shape[1])
@@ -526,6 +665,8 @@ class GpuBackend(Backend):
         return p
 
     def prefix_product(self, a):
+        if self.sharing is not None and a.shape[0] > 1:
+            return self._share_call("partial_products", a)
         a = a.contiguous()
         out = self.torch.empty_like(a)
         for ln in range(a.shape[0]):
@@ -533,6 +674,8 @@ class GpuBackend(Backend):
         return out
 
     def inverse(self, a):
+        if self.sharing is not None and a.shape[0] > 1:
+            return self._share_call("batch_inv", a)
         a = a.contiguous()
         out = self.torch.empty_like(a)
         self.ctx.fr_batch_inverse(a.data_ptr(), n=a.shape[0] * a.shape[1], out=out.data_ptr(), mem=self.M)
@@ -633,8 +776,56 @@ def vanishing(size: int, point: int) -> int:
 
 def shared_copy(B: Backend, a_public):
     """The same values on every lane: the reference's king_share stand-in hands every party the value itself
-    (gsz20/mod.rs:190-213); for SPDZ benchmarks the lanes are filled the same way (values do not affect the work)."""
+    (gsz20/mod.rs:190-213); for SPDZ benchmarks the lanes are filled the same way (values do not affect the work).  On a backend with a real
+    `sharing` that would be no sharing of the value: there it goes on the lifting lanes (the king's), zero elsewhere -- from_public."""
+    if getattr(B, "sharing", None) is not None:
+        return B.lifted(a_public)
     return B.lane_stack([a_public] * B.lanes)
+
+
+def open_shared_proof(B: Backend, out: dict) -> dict:
+    """What the parties do at the end of a proof made on a backend with `sharing`: every commitment, opening proof and evaluation that is on share
+    lanes is opened -- the sum of the `sh` lanes (commitments: Context.points_sum) -- and every `mac` lane sum is checked against it (0 / 1 key:
+    the sums are equal).  Returns a proof of the one-lane shape plonk.verify / marlin.verify take; public entries pass through.  SharingError
+    when a MAC does not match.  All lanes on one backend only: with Sharing(rank=...) the parties hold one lane set each, and opening a proof is
+    an exchange of group elements, which this module does not make."""
+    S = B.sharing
+    if S is None or S.rank is not None:
+        raise ValueError("open_shared_proof needs a backend that holds every party's lanes (sharing=Sharing(...) without rank)")
+    sh, mac = list(range(0, S.lanes, S.lpp)), list(range(1, S.lanes, S.lpp)) if S.lpp == 2 else []
+    g1 = B.czk.CZK_G1
+
+    def points(c, label):
+        aff, inf = np.asarray(c[0], dtype=np.uint64), np.asarray(c[1], dtype=np.uint8)
+        if aff.shape[0] != S.lanes:
+            return c
+        val = B.ctx.points_sum(g1, aff[sh], [0, len(sh)], inf=inf[sh])
+        if mac:
+            m = B.ctx.points_sum(g1, aff[mac], [0, len(mac)], inf=inf[mac])
+            if bool(val[1][0]) != bool(m[1][0]) or (not val[1][0] and not np.array_equal(val[0], m[0])):
+                raise SharingError(f"{label}: the mac lanes do not open to the commitment")
+        return val
+
+    def value(v, label):
+        v = np.asarray(v, dtype=np.uint64).reshape(-1, 4)
+        if v.shape[0] != S.lanes:
+            return v
+        tot = sum(unmont(v[ln]) for ln in sh) % R_MOD
+        if mac and sum(unmont(v[ln]) for ln in mac) % R_MOD != tot:
+            raise SharingError(f"{label}: the mac lanes do not open to the value")
+        return mont(tot).reshape(1, 4)
+
+    def walk(x, label):
+        if isinstance(x, dict):
+            return {k: (value(v, label + "." + k) if k == "value" and not isinstance(v, dict) else walk(v, label + "." + k)) for k, v in x.items()}
+        if isinstance(x, tuple) and len(x) == 2 and all(isinstance(a, np.ndarray) for a in x) and x[0].ndim == 2 and x[0].shape[1] == 12:
+            return points(x, label)
+        if isinstance(x, (list, tuple)):
+            return type(x)(walk(v, label) for v in x)
+        if isinstance(x, np.ndarray) and x.shape == (S.lanes, 4):                  # an evaluation outside an opening (Marlin's evals_*, random_v)
+            return value(x, label)
+        return x
+    return walk(out, "proof")
 
 
 def plonk_inputs(B: Backend, n_gates: int, seed: int = 0x9107) -> dict:
@@ -919,7 +1110,15 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
         # just publicized (:155-157, :228-231) -- the first entries of the two evaluation lists, settled by the transcript point above like everything else, so
         # the real path has the benchmark's synchronisation points and no others.  Lane 0 (every lane is the plain prover when the caller lifts public data onto
         # all of them).  The LCTerm::One constants go to out["lc_consts"]: they do not enter the opened polynomials, the verifier moves them to the evaluation side.
-        val = lambda pend: unmont(resolved(pend)[0])            # noqa: E731
+        # On a backend with a real `sharing` an evaluation of a share polynomial is publicized first: the sum of its sh lanes (open_shared_proof checks
+        # the same values against their mac lanes).
+        sharing = getattr(B, "sharing", None)
+
+        def val(pend):
+            v = resolved(pend)
+            if sharing is not None and v.shape[0] == sharing.lanes:
+                return sum(unmont(v[ln]) for ln in range(0, sharing.lanes, sharing.lpp)) % R_MOD
+            return unmont(v[0])
         inv = lambda v: pow(v % R_MOD, -1, R_MOD)                # noqa: E731
         eb, eg = out["evals_beta"], out["evals_gamma"]
         z_b_beta, t_beta, g_1_beta = val(eb[0]), val(eb[1]), val(eb[2])

@@ -371,6 +371,55 @@ int czk_spdz_batch_open(czk_net* net, const uint64_t* sh, const uint64_t* mac, c
 int czk_add_batch_open(czk_net* net, const uint64_t* val, size_t n, uint64_t* out_value);
 int czk_gsz_batch_open(czk_net* net, const uint64_t* val, size_t n, const uint32_t* degrees, unsigned degree, uint64_t* out_value,
                        uint64_t* out_bad);
+/* ---- products, inverses and running products of SHARED vectors (mpc-algebra/src/share/field.rs) ------------------------------------ */
+/* FieldShare::batch_mul (:97-127), batch_inv (:135-148) and partial_products (:163-182) as one call each on device lanes, for additive shares
+ * (lpp = 1 lane per party) and SPDZ shares (lpp = 2: lane lpp p = party p's sh, lane lpp p + 1 = its mac -- czk_spdz_open_combine's order).
+ * batch_div is czk_share_batch_mul after czk_share_batch_inv.  GSZ shares are not covered.
+ *   lanes form (czk_share_*)     all `parties` (1..32) parties' lanes on this GPU: every vector is L = lpp parties lanes.  Nothing leaves the device
+ *                                but the two counts.  mac_shares: parties x 4 limbs, one Montgomery Fr per party, HOST (NULL allowed for lpp = 1).
+ *   net form (czk_net_share_*)   one party per communicator: every vector is this party's lpp lanes; the opens go through czk_add_batch_open
+ *                                (lpp = 1) / czk_spdz_batch_open (lpp = 2) with `flags`.  mac_share: this party's Montgomery Fr, HOST.
+ * Operands and `out`: n Fr per lane, lanes n elements apart.  Material: the caller's correlated randomness in the same lane order, T triples
+ * (tx, ty, tz with tz = tx ty) resp. P pairs (pb, pc) of BeaverSource::inv_pair per lane, lanes T resp. P elements apart, consumed in the
+ * reference's order (czk_share_material_counts reports T and P):
+ *   CZK_SHARE_OP_MUL               T = n, P = 0
+ *   CZK_SHARE_OP_INV               T = n, P = n       pair i is (b, c) of element i; triple i multiplies x_i b_i
+ *   CZK_SHARE_OP_PARTIAL_PRODUCTS  T = 4 n, P = 2 n + 1   pairs [0, n] are (m, m_inv), pairs [n + 1, 2 n] the inner batch_inv's; triples [0, n) m x,
+ *                                  [n, 2 n) (m x) m_inv, [2 n, 3 n) m_0 m_inv, [3 n, 4 n) the inner batch_inv's product
+ * The calls apply the reference's formulas to whatever pairs they are given.  Its only source hands out (1, 1); for the results to be the inverse
+ * and the running products with random material, each slot needs the relation its formula uses: (m, m_inv) are inverses, m m_inv = 1, and a
+ * batch_inv pair is a mask and itself, c = b (c / open(x b) = 1 / x).
+ * Values (every lane equals the reference's for that party, limb for limb; a public addend v goes to the king's sh lane and as mac_share_p v to
+ * party p's mac lane, share/spdz.rs:204-208):
+ *   batch_mul          out = tz - ty open(x + tx) - tx open(y + ty) + shift(open(x + tx) open(y + ty)).  The two opens are independent: they run as ONE open
+ *                      of the 2 n-element concatenation (same values; the net form counts half the reference's broadcasts in czk_net_stats).
+ *   batch_inv          out = c open(batch_mul(x, b))^-1
+ *   partial_products   out_i = shares of x_0 ... x_i, exactly :163-182
+ * *out_bad (host): opened elements whose MAC check failed, over all opens of the call (always 0 for lpp = 1; the reference asserts 0).
+ * *out_zero (host): opened values that had to be inverted and were zero (the reference unwraps): that element's output is zero on every lane, as
+ * czk_fr_batch_inverse keeps zeros.  Always 0 for batch_mul.  Both are read back at the end of the call (it blocks, like the opens).
+ * n = 0 or parties = 0: CZK_OK, nothing touched but the counts.  NULL vectors with work to do, lpp not 1 or 2, parties > 32: CZK_ERR_ARG; lane
+ * arrays whose byte count overflows: CZK_ERR_SIZE.  `out` must not overlap an input.  Workspace comes from the context's staging pool. */
+#define CZK_SHARE_OP_MUL 0
+#define CZK_SHARE_OP_INV 1
+#define CZK_SHARE_OP_PARTIAL_PRODUCTS 2
+int czk_share_material_counts(int op, size_t n, size_t* triples, size_t* pairs);
+int czk_share_batch_mul(czk_ctx* ctx, size_t lpp, size_t parties, const uint64_t* mac_shares, const uint64_t* x, const uint64_t* y, const uint64_t* tx,
+                        const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_share_batch_inv(czk_ctx* ctx, size_t lpp, size_t parties, const uint64_t* mac_shares, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
+                        const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_share_partial_products(czk_ctx* ctx, size_t lpp, size_t parties, const uint64_t* mac_shares, const uint64_t* x, const uint64_t* pb,
+                               const uint64_t* pc, const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, uint64_t* out_bad,
+                               uint64_t* out_zero);
+int czk_net_share_batch_mul(czk_net* net, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* y, const uint64_t* tx,
+                            const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, int flags, uint64_t* out_bad, uint64_t* out_zero);
+int czk_net_share_batch_inv(czk_net* net, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
+                            const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, int flags, uint64_t* out_bad,
+                            uint64_t* out_zero);
+int czk_net_share_partial_products(czk_net* net, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
+                                   const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, int flags, uint64_t* out_bad,
+                                   uint64_t* out_zero);
+
 /* The king's side of king_compute (mpc-algebra/src/channel.rs:77-80; gsz20's degree reduction, share/gsz20/mod.rs:470-500): every
  * party's n Fr to the king, who receives world x n (device, party order) -- czk_net_send_to_king on Fr lanes -- and the way back. */
 int czk_fr_send_to_king(czk_net* net, const uint64_t* x, size_t n, uint64_t* gathered);

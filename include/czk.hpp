@@ -94,8 +94,39 @@ class Context {
         check(czk_fr_vec_commit(ctx_, a, lanes, n, stride, rand32.data(), out.data(), mem));
         return out;
     }
+    // FieldShare::batch_mul / batch_inv / partial_products (share/field.rs:97-182) with every party's lanes on this GPU (czk_share_*, czk.h): device
+    // pointers, lpp * parties lanes per vector, one mac share per party.  A failed MAC check panics like the reference's assert, a zero divisor like
+    // its unwrap.
+    struct ShareCounts { uint64_t bad = 0, zero = 0; };
+    void share_material_counts(int op, size_t n, size_t* triples, size_t* pairs) const { check(czk_share_material_counts(op, n, triples, pairs)); }
+    void share_batch_mul(size_t lpp, size_t parties, const std::vector<Fr>& mac_shares, const uint64_t* x, const uint64_t* y, const uint64_t* tx,
+                         const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n) const {
+        ShareCounts c;
+        check(czk_share_batch_mul(ctx_, lpp, parties, mac_limbs(mac_shares, lpp, parties), x, y, tx, ty, tz, out, n, &c.bad, &c.zero));
+        share_assert(c, "batch_mul");
+    }
+    void share_batch_inv(size_t lpp, size_t parties, const std::vector<Fr>& mac_shares, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
+                         const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n) const {
+        ShareCounts c;
+        check(czk_share_batch_inv(ctx_, lpp, parties, mac_limbs(mac_shares, lpp, parties), x, pb, pc, tx, ty, tz, out, n, &c.bad, &c.zero));
+        share_assert(c, "batch_inv");
+    }
+    void share_partial_products(size_t lpp, size_t parties, const std::vector<Fr>& mac_shares, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
+                                const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n) const {
+        ShareCounts c;
+        check(czk_share_partial_products(ctx_, lpp, parties, mac_limbs(mac_shares, lpp, parties), x, pb, pc, tx, ty, tz, out, n, &c.bad, &c.zero));
+        share_assert(c, "partial_products");
+    }
+    static void share_assert(const ShareCounts& c, const char* what) {
+        if (c.bad) throw Panic(CZK_ERR_CHECK, std::string(what) + ": assertion failed: sum.is_zero() (SPDZ MAC check, share/spdz.rs:183) on " + std::to_string(c.bad) + " values");
+        if (c.zero) throw Panic(CZK_ERR_CHECK, std::string(what) + ": called `Option::unwrap()` on a `None` value (inverse of zero, share/field.rs:141) on " + std::to_string(c.zero) + " values");
+    }
 
   private:
+    static const uint64_t* mac_limbs(const std::vector<Fr>& mac_shares, size_t lpp, size_t parties) {
+        if (lpp == 2 && mac_shares.size() < parties) throw Panic(CZK_ERR_ARG, "one mac share per party");
+        return mac_shares.empty() ? nullptr : mac_shares[0].l;
+    }
     czk_ctx* ctx_ = nullptr;
 };
 
@@ -233,6 +264,25 @@ class Net {
     }
     //   AdditiveFieldShare::batch_open (share/add.rs:256-259)
     void add_batch_open(const uint64_t* val, size_t n, uint64_t* out) const { check(czk_add_batch_open(n_, val, n, out)); }
+    //   FieldShare::batch_mul / batch_inv / partial_products on this party's lpp lanes (czk_net_share_*, czk.h); flags as czk_spdz_batch_open's
+    void share_batch_mul(size_t lpp, const Fr& mac_share, const uint64_t* x, const uint64_t* y, const uint64_t* tx, const uint64_t* ty, const uint64_t* tz,
+                         uint64_t* out, size_t n, int flags = CZK_OPEN_COMMIT) const {
+        Context::ShareCounts c;
+        check(czk_net_share_batch_mul(n_, lpp, mac_share.l, x, y, tx, ty, tz, out, n, flags, &c.bad, &c.zero));
+        Context::share_assert(c, "batch_mul");
+    }
+    void share_batch_inv(size_t lpp, const Fr& mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc, const uint64_t* tx, const uint64_t* ty,
+                         const uint64_t* tz, uint64_t* out, size_t n, int flags = CZK_OPEN_COMMIT) const {
+        Context::ShareCounts c;
+        check(czk_net_share_batch_inv(n_, lpp, mac_share.l, x, pb, pc, tx, ty, tz, out, n, flags, &c.bad, &c.zero));
+        Context::share_assert(c, "batch_inv");
+    }
+    void share_partial_products(size_t lpp, const Fr& mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc, const uint64_t* tx,
+                                const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, int flags = CZK_OPEN_COMMIT) const {
+        Context::ShareCounts c;
+        check(czk_net_share_partial_products(n_, lpp, mac_share.l, x, pb, pc, tx, ty, tz, out, n, flags, &c.bad, &c.zero));
+        Context::share_assert(c, "partial_products");
+    }
     //   GszFieldShare::batch_open (share/gsz20/mod.rs:286-300) with one degree bound for the whole vector
     void gsz_batch_open(const uint64_t* val, size_t n, unsigned degree, uint64_t* out) const {
         uint64_t bad = 0;

@@ -78,6 +78,9 @@ pub const CZK_COMMIT_LEAF_ELEMS: c_int = 32; // #define
 pub const CZK_COMMIT_FANOUT: c_int = 32; // #define
 pub const CZK_OPEN_COMMIT: c_int = 1; // #define
 pub const CZK_OPEN_COMMIT_TREE: c_int = 2; // #define
+pub const CZK_SHARE_OP_MUL: c_int = 0; // #define
+pub const CZK_SHARE_OP_INV: c_int = 1; // #define
+pub const CZK_SHARE_OP_PARTIAL_PRODUCTS: c_int = 2; // #define
 
 #[link(name = "czk_hip")]
 extern "C" {
@@ -137,6 +140,13 @@ extern "C" {
     pub fn czk_spdz_batch_open(net: *mut czk_net, sh: *const u64, mac: *const u64, mac_share: *const u64, n: usize, out_value: *mut u64, flags: c_int, out_bad: *mut u64) -> c_int;
     pub fn czk_add_batch_open(net: *mut czk_net, val: *const u64, n: usize, out_value: *mut u64) -> c_int;
     pub fn czk_gsz_batch_open(net: *mut czk_net, val: *const u64, n: usize, degrees: *const u32, degree: c_uint, out_value: *mut u64, out_bad: *mut u64) -> c_int;
+    pub fn czk_share_material_counts(op: c_int, n: usize, triples: *mut usize, pairs: *mut usize) -> c_int;
+    pub fn czk_share_batch_mul(ctx: *mut czk_ctx, lpp: usize, parties: usize, mac_shares: *const u64, x: *const u64, y: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_share_batch_inv(ctx: *mut czk_ctx, lpp: usize, parties: usize, mac_shares: *const u64, x: *const u64, pb: *const u64, pc: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_share_partial_products(ctx: *mut czk_ctx, lpp: usize, parties: usize, mac_shares: *const u64, x: *const u64, pb: *const u64, pc: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_net_share_batch_mul(net: *mut czk_net, lpp: usize, mac_share: *const u64, x: *const u64, y: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, flags: c_int, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_net_share_batch_inv(net: *mut czk_net, lpp: usize, mac_share: *const u64, x: *const u64, pb: *const u64, pc: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, flags: c_int, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_net_share_partial_products(net: *mut czk_net, lpp: usize, mac_share: *const u64, x: *const u64, pb: *const u64, pc: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, flags: c_int, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
     pub fn czk_fr_send_to_king(net: *mut czk_net, x: *const u64, n: usize, gathered: *mut u64) -> c_int;
     pub fn czk_fr_recv_from_king(net: *mut czk_net, parts: *const u64, n: usize, out: *mut u64) -> c_int;
     pub fn czk_gsz_batch_king_compute(net: *mut czk_net, val: *const u64, n: usize, degrees: *const u32, degree: c_uint, out: *mut u64, out_bad: *mut u64) -> c_int;
