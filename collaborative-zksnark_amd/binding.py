@@ -150,6 +150,8 @@ LAB_ARITH_PROBE_OPS = {
     "teu_from_niels": (40, 42, 56), "teu_madd": (41, 98, 56), "teu_add": (42, 112, 56), "teu_double": (43, 56, 56), "teu_to_jac": (44, 56, 36),
     "te_load_niels": (45, 52, 42),
     "p2_mul": (50, 57, 28), "xyzzu2_add": (51, 226, 113), "xyzzu2_double": (52, 113, 113), "xyzzu2_acc_mixed": (53, 168, 113),
+    "fqu_mul_s": (70, 28, 14), "fqu_sqr_s": (71, 14, 14), "fqu_mul_add_s": (72, 56, 14), "fqu_mul_add_hi_s": (73, 70, 14),
+    "fqu_mul_hi_s": (74, 42, 14), "fqu_mul_add4_s": (75, 112, 14),
     "fru_mul": (60, 18, 9), "fru_normalize": (62, 9, 9), "fru_unpack": (63, 8, 9), "fru_pack": (64, 9, 8), "fru_reduce_2r": (65, 9, 9),
     "fru_canon": (66, 9, 8), "fru_canon_mulout": (67, 9, 8), "fru_add": (68, 18, 9),
 }

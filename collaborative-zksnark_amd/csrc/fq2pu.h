@@ -48,7 +48,9 @@ __device__ __forceinline__ P2B p2_b(const FqU& b) {
     const FqU n5 = fqu_neg5<BIG>(oth);
     return P2B{fqu_select(par, oth, b), fqu_select(par, b, n5)};
 }
-__device__ __forceinline__ FqU p2_mul(const P2A& a, const P2B& b) { return fqu_mul_add(a.own, b.x, a.oth, b.y); }
+// (signed columns: at every call site of this file the multiplicand's limbs stay below 2^29 -- normalised values and K p - x with K <= 8 --
+// so a column holds less than 28 * 2^57; tests/test_fqu_subtractive_cpu.py)
+__device__ __forceinline__ FqU p2_mul(const P2A& a, const P2B& b) { return fqu_mul_add_s(a.own, b.x, a.oth, b.y); }
 __device__ __forceinline__ bool pair_all(bool c) {
     const u32 v = c ? 1u : 0u;
     return (v & pair_swap_u32(v)) != 0;
@@ -156,7 +158,7 @@ __device__ __forceinline__ void xyzzu2_add(XYZZU2& a, const XYZZU2& b) {
 #pragma unroll
     for (int i = 0; i < 14; i++) ns1.l[i] = fqu_8p(i) - s1.l[i];
     const P2A nsa = p2_a(ns1);
-    a.y = fqu_mul_add4(ra.own, db.x, ra.oth, db.y, nsa.own, p3b.x, nsa.oth, p3b.y);   // R (Q - X3) - S1 PPP, one reduction
+    a.y = fqu_mul_add4_s(ra.own, db.x, ra.oth, db.y, nsa.own, p3b.x, nsa.oth, p3b.y);   // R (Q - X3) - S1 PPP, one reduction
 }
 // a = 2 a (dbl-2008-s-1, a = 0).  U = 2 Y1 == 0 (a point of order two) goes through the complete formulas, which return infinity.
 __device__ __forceinline__ void xyzzu2_double(XYZZU2& a) {
@@ -192,7 +194,7 @@ __device__ __forceinline__ void xyzzu2_double(XYZZU2& a) {
     for (int i = 0; i < 14; i++) nw.l[i] = fqu_8p(i) - w.l[i];           // 8 p - W (lazy)
     const P2A nwa = p2_a(nw);
     const P2B yb = p2_b<true>(a.y);
-    const FqU y3 = fqu_mul_add4(ma.own, db.x, ma.oth, db.y, nwa.own, yb.x, nwa.oth, yb.y);   // M (S - X3) - W Y1
+    const FqU y3 = fqu_mul_add4_s(ma.own, db.x, ma.oth, db.y, nwa.own, yb.x, nwa.oth, yb.y);   // M (S - X3) - W Y1
     a.zz = p2_mul(p2_a(v), p2_b<false>(a.zz));
     a.zzz = p2_mul(p2_a(w), p2_b<false>(a.zzz));
     a.x = x3;
@@ -231,7 +233,7 @@ __device__ __forceinline__ bool xyzzu2_acc_mixed(FqU& ax, FqU& ay, FqU& azz, FqU
 #pragma unroll
     for (int i = 0; i < 14; i++) nay.l[i] = fqu_8p(i) - ay.l[i];
     const P2A na = p2_a(nay);
-    ay = fqu_mul_add4(ra.own, db.x, ra.oth, db.y, na.own, p3b.x, na.oth, p3b.y);   // R (Q - X3) - Y1 PPP, one reduction
+    ay = fqu_mul_add4_s(ra.own, db.x, ra.oth, db.y, na.own, p3b.x, na.oth, p3b.y);   // R (Q - X3) - Y1 PPP, one reduction
     ax = x3;
     azz = zz3;
     azzz = zzz3;

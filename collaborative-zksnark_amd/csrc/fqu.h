@@ -527,9 +527,125 @@ struct MadUS<14> {
     }
 };
 
+// ---------------------------------------------------------------------------------------------
+// The SUBTRACTIVE column reduction (the `_s` multiplies below).  The additive loop adds m p with m = -T / p mod R' and pays, per
+// quotient column, a negation, a mask, a 64-bit `+ FQU_MASK` and the shift.  p == 1 mod 2^28, so SUBTRACTING q p with q = T / p mod R'
+// needs only the mask and the shift: the digit is t = acc & FQU_MASK, acc - t p_0 has a zero low limb, and an ARITHMETIC acc >> 28 is
+// the exact quotient.  The products t_i (-p_j), j >= 1, are v_mad_i64_i32 against the negated limbs of p in scalar registers; the
+// accumulator is read as a signed 64-bit value (wrap-around between the products of a column is harmless: only the column's final
+// value must lie in [-2^63, 2^63)).
+// Same integer as the additive form: that one returns (T - q p) / R' + p [q != 0].  The + p comes from the TOP digit, taken as
+// t_13 - 2^28 (a negative multiplier: it adds p 2^392 to the numerator) exactly when some digit is non-zero -- seven v_or3 / v_or, one
+// v_sub and one v_and_or per multiplication.  So every value bound and closure proof of the additive form holds unchanged.
+// Contract (DESIGN 4a "signed columns"): sum a_i b_j of a column + its carry (+ e) < 2^63 - 2^60; the negative part is above -13 * 2^56.
+// tests/test_fqu_subtractive_cpu.py proves it for every call site of an `_s` multiply and lists the sites that must stay additive.
+// -DCZK_FQU_ADDITIVE (A/B builds only) compiles every `_s` multiply as its additive twin.
+// ---------------------------------------------------------------------------------------------
+#ifdef CZK_FQU_ADDITIVE
+constexpr bool FQU_SIGNED = false;
+#else
+constexpr bool FQU_SIGNED = true;
+#endif
+__device__ __forceinline__ u32 fqu_neg_p(int i) { return 0u - fqu_p(i); }   // -p_i as a 32-bit two's-complement multiplier (i >= 1)
+// acc += sum_t x[t] * y[t], signed: x a 28-bit digit (the top one may be negative), y = -p_j in a scalar register
+template <int CNT>
+struct MadIS;
+#define FQU_MI(A, B) "v_mad_i64_i32 %0, vcc, %" #A ", %" #B ", %0"
+#define FQU_NL "\n\t"
+#define FQU_OP(T) "v"(x[T]), "s"(y[T])
+#define FQU_MADIS(CNT, ASM, ...)                                                           \
+    template <>                                                                            \
+    struct MadIS<CNT> {                                                                    \
+        static __device__ __forceinline__ void run(u64& a, const u32* x, const u32* y) {  \
+            asm(ASM : "+v"(a) : __VA_ARGS__ : "vcc");                                      \
+        }                                                                                  \
+    };
+#define FQU_MI2 FQU_MI(1, 2) FQU_NL FQU_MI(3, 4)
+#define FQU_MI4 FQU_MI2 FQU_NL FQU_MI(5, 6) FQU_NL FQU_MI(7, 8)
+#define FQU_MI6 FQU_MI4 FQU_NL FQU_MI(9, 10) FQU_NL FQU_MI(11, 12)
+#define FQU_MI8 FQU_MI6 FQU_NL FQU_MI(13, 14) FQU_NL FQU_MI(15, 16)
+#define FQU_MI10 FQU_MI8 FQU_NL FQU_MI(17, 18) FQU_NL FQU_MI(19, 20)
+#define FQU_MI12 FQU_MI10 FQU_NL FQU_MI(21, 22) FQU_NL FQU_MI(23, 24)
+#define FQU_OP2 FQU_OP(0), FQU_OP(1)
+#define FQU_OP4 FQU_OP2, FQU_OP(2), FQU_OP(3)
+#define FQU_OP6 FQU_OP4, FQU_OP(4), FQU_OP(5)
+#define FQU_OP8 FQU_OP6, FQU_OP(6), FQU_OP(7)
+#define FQU_OP10 FQU_OP8, FQU_OP(8), FQU_OP(9)
+#define FQU_OP12 FQU_OP10, FQU_OP(10), FQU_OP(11)
+FQU_MADIS(1, FQU_MI(1, 2), FQU_OP(0))
+FQU_MADIS(2, FQU_MI2, FQU_OP2)
+FQU_MADIS(3, FQU_MI2 FQU_NL FQU_MI(5, 6), FQU_OP2, FQU_OP(2))
+FQU_MADIS(4, FQU_MI4, FQU_OP4)
+FQU_MADIS(5, FQU_MI4 FQU_NL FQU_MI(9, 10), FQU_OP4, FQU_OP(4))
+FQU_MADIS(6, FQU_MI6, FQU_OP6)
+FQU_MADIS(7, FQU_MI6 FQU_NL FQU_MI(13, 14), FQU_OP6, FQU_OP(6))
+FQU_MADIS(8, FQU_MI8, FQU_OP8)
+FQU_MADIS(9, FQU_MI8 FQU_NL FQU_MI(17, 18), FQU_OP8, FQU_OP(8))
+FQU_MADIS(10, FQU_MI10, FQU_OP10)
+FQU_MADIS(11, FQU_MI10 FQU_NL FQU_MI(21, 22), FQU_OP10, FQU_OP(10))
+FQU_MADIS(12, FQU_MI12, FQU_OP12)
+FQU_MADIS(13, FQU_MI12 FQU_NL FQU_MI(25, 26), FQU_OP12, FQU_OP(12))
+#undef FQU_OP12
+#undef FQU_OP10
+#undef FQU_OP8
+#undef FQU_OP6
+#undef FQU_OP4
+#undef FQU_OP2
+#undef FQU_MI12
+#undef FQU_MI10
+#undef FQU_MI8
+#undef FQU_MI6
+#undef FQU_MI4
+#undef FQU_MI2
+#undef FQU_MADIS
+#undef FQU_OP
+#undef FQU_NL
+#undef FQU_MI
+
+// The tail of one column, shared by every multiply below: m[] holds the quotient digits, acc the column.  k < 14: takes digit k and
+// carries; k >= 14: the caller has stored the result limb, this only carries.
+template <bool SUB, int k>
+__device__ __forceinline__ void fqu_column_step(u32 (&m)[14], u64& acc) {
+    if constexpr (!SUB) {
+        if constexpr (k < 14) {
+            m[k] = (0u - (u32)acc) & FQU_MASK;   // -p^-1 == -1 mod 2^28
+            acc += FQU_MASK;                     // == (acc + m[k] * p[0]) after the shift below: carries out of the low 28 bits iff they are non-zero
+                                                 // (and needs no zero-extended copy of m[k]: one v_mov per column less)
+        }
+        acc >>= 28;
+    } else {
+        if constexpr (k < 14) m[k] = (u32)acc & FQU_MASK;   // p^-1 == 1 mod 2^28; the low limb of acc - m[k] p[0] is zero, so the shift alone divides
+        if constexpr (k == 13) {
+            u32 any = m[0];
+#pragma unroll
+            for (int i = 1; i < 14; i++) any |= m[i];
+            m[13] |= (0u - any) & ~FQU_MASK;     // q != 0: the top digit becomes t_13 - 2^28 (0 < any < 2^28 sets the four high bits of -any)
+            asm("v_mad_i64_i32 %0, vcc, %1, -1, %0" : "+v"(acc) : "v"(m[13]) : "vcc");   // - (t_13 - 2^28) p_0: zero low limb, and the + 1 of the carry
+        }
+        acc = (u64)((long long)acc >> 28);
+    }
+}
+// the reduction products of column k: acc += sum m_i p_(k - i) (additive) or sum m_i (-p_(k - i)) (signed), p's limbs from scalar registers
+template <bool SUB, int k>
+__device__ __forceinline__ void fqu_column_reduce(const u32 (&m)[14], u64& acc) {
+    constexpr int N = 14;
+    constexpr int i0 = k < N ? 0 : k - N + 1;
+    constexpr int cmp = (k < N ? k - 1 : N - 1) - i0 + 1;
+    if constexpr (cmp > 0) {
+        u32 xs[cmp], ys[cmp];
+#pragma unroll
+        for (int t = 0; t < cmp; t++) {
+            xs[t] = m[i0 + t];
+            ys[t] = SUB ? fqu_neg_p(k - i0 - t) : fqu_p(k - i0 - t);
+        }
+        if constexpr (SUB) MadIS<cmp>::run(acc, xs, ys);
+        else MadUS<cmp>::run(acc, xs, ys);
+    }
+}
+
 // a * b / R' mod p (+ possibly p): operands may be lazy (limbs < 2^30, value < 2^7 p); result limbs normalised
-// (< 2^28, top limb small), value < 1.01 p.
-template <bool HI>
+// (< 2^28, top limb small), value < 1.01 p.  SUB: the signed-column form (contract above).
+template <bool HI, bool SUB = false>
 __device__ __forceinline__ FqU fqu_mul_impl(const FqU& a, const FqU& b, const FqU& e) {
     constexpr int N = 14;
     u32 m[N];
@@ -549,25 +665,12 @@ __device__ __forceinline__ FqU fqu_mul_impl(const FqU& a, const FqU& b, const Fq
             if constexpr (k == 0) acc = mad_first(xs[0], ys[0]);
             else MadU<cab>::run(acc, xs, ys);
         }
-        constexpr int cmp = (k < N ? k - 1 : N - 1) - i0 + 1;
-        if constexpr (cmp > 0) {
-            u32 xs[cmp], ys[cmp];
-#pragma unroll
-            for (int t = 0; t < cmp; t++) {
-                xs[t] = m[i0 + t];
-                ys[t] = fqu_p(k - i0 - t);
-            }
-            MadUS<cmp>::run(acc, xs, ys);   // p's limbs from scalar registers
-        }
-        if constexpr (k < N) {
-            m[k] = (0u - (u32)acc) & FQU_MASK;   // -p^-1 == -1 mod 2^28
-            acc += FQU_MASK;                     // == (acc + m[k] * p[0]) after the shift below: carries out of the low 28 bits iff they are non-zero
-                                                 // (and needs no zero-extended copy of m[k]: one v_mov per column less)
-        } else {
+        fqu_column_reduce<SUB, k>(m, acc);
+        if constexpr (k >= N) {
             if constexpr (HI) acc += e.l[k - N];
             r.l[k - N] = (u32)acc & FQU_MASK;
         }
-        acc >>= 28;
+        fqu_column_step<SUB, k>(m, acc);
     });
     r.l[N - 1] = (u32)acc;
     if constexpr (HI) r.l[N - 1] += e.l[N - 1];
@@ -575,11 +678,15 @@ __device__ __forceinline__ FqU fqu_mul_impl(const FqU& a, const FqU& b, const Fq
 }
 __device__ __forceinline__ FqU fqu_mul(const FqU& a, const FqU& b) { return fqu_mul_impl<false>(a, b, a); }
 __device__ __forceinline__ FqU fqu_mul_hi(const FqU& a, const FqU& b, const FqU& e) { return fqu_mul_impl<true>(a, b, e); }   // a b / R' + e, normalised (see fqu_mul_add_hi)
+// the same values through signed columns: for call sites whose column sums stay below 2^63 - 2^60
+__device__ __forceinline__ FqU fqu_mul_s(const FqU& a, const FqU& b) { return fqu_mul_impl<false, FQU_SIGNED>(a, b, a); }
+__device__ __forceinline__ FqU fqu_mul_hi_s(const FqU& a, const FqU& b, const FqU& e) { return fqu_mul_impl<true, FQU_SIGNED>(a, b, e); }
 
 // a * a / R' mod p: 105 products instead of 196 (off-diagonal terms once, against the doubled operand).  Same operand
 // range as fqu_mul(a, a): limbs < 2^30, so the doubled limbs fit 31 bits and a column holds at most
 // 7 * 2^61 + 2^60 + 13 * 2^56 < 2^64.
-__device__ __forceinline__ FqU fqu_sqr(const FqU& a) {
+template <bool SUB>
+__device__ __forceinline__ FqU fqu_sqr_impl(const FqU& a) {
     constexpr int N = 14;
     u32 m[N], a2[N];
 #pragma unroll
@@ -605,32 +712,20 @@ __device__ __forceinline__ FqU fqu_sqr(const FqU& a) {
             if constexpr (k == 0) acc = mad_first(xs[0], ys[0]);
             else MadU<1>::run(acc, xs, ys);
         }
-        constexpr int cmp = (k < N ? k - 1 : N - 1) - i0 + 1;
-        if constexpr (cmp > 0) {
-            u32 xs[cmp], ys[cmp];
-#pragma unroll
-            for (int t = 0; t < cmp; t++) {
-                xs[t] = m[i0 + t];
-                ys[t] = fqu_p(k - i0 - t);
-            }
-            MadUS<cmp>::run(acc, xs, ys);   // p's limbs from scalar registers
-        }
-        if constexpr (k < N) {
-            m[k] = (0u - (u32)acc) & FQU_MASK;
-            acc += FQU_MASK;                     // see fqu_mul
-        } else {
-            r.l[k - N] = (u32)acc & FQU_MASK;
-        }
-        acc >>= 28;
+        fqu_column_reduce<SUB, k>(m, acc);
+        if constexpr (k >= N) r.l[k - N] = (u32)acc & FQU_MASK;
+        fqu_column_step<SUB, k>(m, acc);
     });
     r.l[N - 1] = (u32)acc;
     return r;
 }
+__device__ __forceinline__ FqU fqu_sqr(const FqU& a) { return fqu_sqr_impl<false>(a); }
+__device__ __forceinline__ FqU fqu_sqr_s(const FqU& a) { return fqu_sqr_impl<FQU_SIGNED>(a); }   // signed columns: limbs of a up to 2^29.4 (see fqu_mul_s)
 
 // (a * b + c * d) / R' mod p with ONE Montgomery reduction (saves 182 of 756 multiply-adds).  Column capacity: the
 // caller guarantees limb(a) * limb(b) < 2^58 and limb(c) * limb(d) < 2^58 (one factor of each product normalised),
 // so a column holds < 28 * 2^58 + 13 * 2^56 < 2^63.
-template <bool HI>
+template <bool HI, bool SUB = false>
 __device__ __forceinline__ FqU fqu_mul_add_impl(const FqU& a, const FqU& b, const FqU& c, const FqU& d, const FqU& e) {
     constexpr int N = 14;
     u32 m[N];
@@ -656,30 +751,20 @@ __device__ __forceinline__ FqU fqu_mul_add_impl(const FqU& a, const FqU& b, cons
             }
             MadU<cab>::run(acc, xs, ys);
         }
-        constexpr int cmp = (k < N ? k - 1 : N - 1) - i0 + 1;
-        if constexpr (cmp > 0) {
-            u32 xs[cmp], ys[cmp];
-#pragma unroll
-            for (int t = 0; t < cmp; t++) {
-                xs[t] = m[i0 + t];
-                ys[t] = fqu_p(k - i0 - t);
-            }
-            MadUS<cmp>::run(acc, xs, ys);   // p's limbs from scalar registers
-        }
-        if constexpr (k < N) {
-            m[k] = (0u - (u32)acc) & FQU_MASK;
-            acc += FQU_MASK;                     // see fqu_mul
-        } else {
+        fqu_column_reduce<SUB, k>(m, acc);
+        if constexpr (k >= N) {
             if constexpr (HI) acc += e.l[k - N];   // the addend rides the column carries: no separate add + normalise pass afterwards
             r.l[k - N] = (u32)acc & FQU_MASK;
         }
-        acc >>= 28;
+        fqu_column_step<SUB, k>(m, acc);
     });
     r.l[N - 1] = (u32)acc;
     if constexpr (HI) r.l[N - 1] += e.l[N - 1];
     return r;
 }
 __device__ __forceinline__ FqU fqu_mul_add(const FqU& a, const FqU& b, const FqU& c, const FqU& d) { return fqu_mul_add_impl<false>(a, b, c, d, a); }
+__device__ __forceinline__ FqU fqu_mul_add_s(const FqU& a, const FqU& b, const FqU& c, const FqU& d) { return fqu_mul_add_impl<false, FQU_SIGNED>(a, b, c, d, a); }   // signed columns (see fqu_mul_s)
+__device__ __forceinline__ FqU fqu_mul_add_hi_s(const FqU& a, const FqU& b, const FqU& c, const FqU& d, const FqU& e) { return fqu_mul_add_impl<true, FQU_SIGNED>(a, b, c, d, e); }
 // (a b + c d) / R' + e with the limbs of e (lazy, < 2^32, any value that keeps the result below 2^392) added into the HIGH columns before they are
 // carried out: the result is the NORMALISED form of mont(a b + c d) + e.  Replaces "multiply, then a limb-wise add / subtract, then a carry pass"
 // (68 instructions per Fq) by 14 limb subtractions that form e and 14 column adds.
@@ -687,8 +772,9 @@ __device__ __forceinline__ FqU fqu_mul_add_hi(const FqU& a, const FqU& b, const 
 
 // (a b + c d + e f + g h) / R' mod p with ONE Montgomery reduction.  Column capacity: every limb product < 2^58
 // (at most one lazy factor, < 2^30, per product), so a column holds < 56 * 2^58 + 13 * 2^56 < 2^64.
-__device__ __forceinline__ FqU fqu_mul_add4(const FqU& a, const FqU& b, const FqU& c, const FqU& d, const FqU& e, const FqU& f, const FqU& g,
-                                            const FqU& h) {
+template <bool SUB>
+__device__ __forceinline__ FqU fqu_mul_add4_impl(const FqU& a, const FqU& b, const FqU& c, const FqU& d, const FqU& e, const FqU& f, const FqU& g,
+                                                 const FqU& h) {
     constexpr int N = 14;
     u32 m[N];
     FqU r;
@@ -725,26 +811,22 @@ __device__ __forceinline__ FqU fqu_mul_add4(const FqU& a, const FqU& b, const Fq
             }
             MadU<cab>::run(acc, xs, ys);
         }
-        constexpr int cmp = (k < N ? k - 1 : N - 1) - i0 + 1;
-        if constexpr (cmp > 0) {
-            u32 xs[cmp], ys[cmp];
-#pragma unroll
-            for (int t = 0; t < cmp; t++) {
-                xs[t] = m[i0 + t];
-                ys[t] = fqu_p(k - i0 - t);
-            }
-            MadUS<cmp>::run(acc, xs, ys);   // p's limbs from scalar registers
-        }
-        if constexpr (k < N) {
-            m[k] = (0u - (u32)acc) & FQU_MASK;
-            acc += FQU_MASK;                     // see fqu_mul
-        } else {
-            r.l[k - N] = (u32)acc & FQU_MASK;
-        }
-        acc >>= 28;
+        fqu_column_reduce<SUB, k>(m, acc);
+        if constexpr (k >= N) r.l[k - N] = (u32)acc & FQU_MASK;
+        fqu_column_step<SUB, k>(m, acc);
     });
     r.l[N - 1] = (u32)acc;
     return r;
+}
+__device__ __forceinline__ FqU fqu_mul_add4(const FqU& a, const FqU& b, const FqU& c, const FqU& d, const FqU& e, const FqU& f, const FqU& g,
+                                            const FqU& h) {
+    return fqu_mul_add4_impl<false>(a, b, c, d, e, f, g, h);
+}
+// signed columns (see fqu_mul_s): four products per term leave room only when most factors are normalised -- the Y3 sites qualify with
+// limb products of 2 x 2^56 + 2 x 2^57 per term
+__device__ __forceinline__ FqU fqu_mul_add4_s(const FqU& a, const FqU& b, const FqU& c, const FqU& d, const FqU& e, const FqU& f, const FqU& g,
+                                              const FqU& h) {
+    return fqu_mul_add4_impl<FQU_SIGNED>(a, b, c, d, e, f, g, h);
 }
 
 // carry-propagate: limbs < 2^28 afterwards (top limb takes the rest)
@@ -818,23 +900,24 @@ __device__ __forceinline__ Fq fqu_pack(const FqU& a) {
 // addition in the saturated form.  (H = U2 - X1 + 16 p lies in (6 p, 18 p); it is 0 mod p only if it equals j p,
 // and p == 1 mod 2^28 makes the low 28 bits of j p equal j.)
 __device__ __forceinline__ bool fqu_xyzz_acc_mixed(FqU& ax, FqU& ay, FqU& azz, FqU& azzz, const FqU& qx, const FqU& qy_lazy) {
-    FqU u2 = fqu_mul(qx, azz);
+    // (signed columns wherever one factor is normalised; the squares of pp and r -- both carry a K p table, limbs up to 2^29.9 -- stay additive)
+    FqU u2 = fqu_mul_s(qx, azz);
     FqU pp = fqu_sub_lazy<16>(u2, ax);
     if (((pp.l[0] & FQU_MASK) - 6u) <= 12u) return false;
-    FqU s2 = fqu_mul(qy_lazy, azzz);
+    FqU s2 = fqu_mul_s(qy_lazy, azzz);
     FqU r = fqu_sub_lazy<8>(s2, ay);
     FqU p2 = fqu_sqr(pp);
-    azz = fqu_mul(azz, p2);
-    FqU p3 = fqu_mul(pp, p2);
-    azzz = fqu_mul(azzz, p3);
-    FqU qv = fqu_mul(ax, p2);
+    azz = fqu_mul_s(azz, p2);
+    FqU p3 = fqu_mul_s(pp, p2);
+    azzz = fqu_mul_s(azzz, p3);
+    FqU qv = fqu_mul_s(ax, p2);
     FqU t = fqu_sqr(r);
     ax = fqu_sub3_norm(t, p3, qv);                       // < 1.01 p + 8 p
     FqU d = fqu_normalize(fqu_sub_lazy<16>(qv, ax));     // Q - X3 + 16 p
     FqU nay;                                             // 8 p - Y1 (lazy): Y3 = r d + (-Y1) PPP, one reduction
 #pragma unroll
     for (int i = 0; i < 14; i++) nay.l[i] = fqu_8p(i) - ay.l[i];
-    ay = fqu_mul_add(r, d, nay, p3);                     // normalised multiply output, < 1.01 p
+    ay = fqu_mul_add_s(r, d, nay, p3);                   // normalised multiply output, < 1.01 p
     return true;
 }
 
@@ -916,28 +999,29 @@ __device__ __forceinline__ void xyzzu_add(XYZZU& a, const XYZZU& b) {
         a = b;
         return;
     }
-    const FqU u1 = fqu_mul(a.x, b.zz);
-    const FqU u2 = fqu_mul(b.x, a.zz);
+    // every product below runs on signed columns: the lazy factors carry at most 4 p (limbs < 2^29.5) or meet a normalised one
+    const FqU u1 = fqu_mul_s(a.x, b.zz);
+    const FqU u2 = fqu_mul_s(b.x, a.zz);
     const FqU pp = fqu_sub_lazy<4>(u2, u1);
     if (((pp.l[0] & FQU_MASK) - 3u) <= 2u) {
         a = xyzzu_add_slow(a, b);
         return;
     }
-    const FqU s1 = fqu_mul(a.y, b.zzz);
-    const FqU s2 = fqu_mul(b.y, a.zzz);
+    const FqU s1 = fqu_mul_s(a.y, b.zzz);
+    const FqU s2 = fqu_mul_s(b.y, a.zzz);
     const FqU r = fqu_sub_lazy<4>(s2, s1);
-    const FqU p2 = fqu_sqr(pp);
-    const FqU p3 = fqu_mul(pp, p2);
-    const FqU qv = fqu_mul(u1, p2);
-    a.zz = fqu_mul(fqu_mul(a.zz, b.zz), p2);
-    a.zzz = fqu_mul(fqu_mul(a.zzz, b.zzz), p3);
-    const FqU t = fqu_sqr(r);
+    const FqU p2 = fqu_sqr_s(pp);
+    const FqU p3 = fqu_mul_s(pp, p2);
+    const FqU qv = fqu_mul_s(u1, p2);
+    a.zz = fqu_mul_s(fqu_mul_s(a.zz, b.zz), p2);
+    a.zzz = fqu_mul_s(fqu_mul_s(a.zzz, b.zzz), p3);
+    const FqU t = fqu_sqr_s(r);
     a.x = fqu_sub3_norm(t, p3, qv);                            // R^2 - PPP - 2 Q + 8 p  < 9.01 p
     const FqU d = fqu_normalize(fqu_sub_lazy<16>(qv, a.x));   // Q - X3 + 16 p
     FqU ns1;                                                   // 8 p - S1 (lazy): Y3 = R d + (-S1) PPP under one reduction
 #pragma unroll
     for (int i = 0; i < 14; i++) ns1.l[i] = fqu_8p(i) - s1.l[i];
-    a.y = fqu_mul_add(r, d, ns1, p3);
+    a.y = fqu_mul_add_s(r, d, ns1, p3);
 }
 // a = 2 a (dbl-2008-s-1, a = 0: 6M + 3S + the fused Y3).  The subgroup has odd order: no point has Y == 0.
 __device__ __forceinline__ void xyzzu_double(XYZZU& a) {
@@ -945,14 +1029,14 @@ __device__ __forceinline__ void xyzzu_double(XYZZU& a) {
     FqU u;
 #pragma unroll
     for (int i = 0; i < 14; i++) u.l[i] = a.y.l[i] + a.y.l[i];            // U = 2 Y1, limbs < 2^29
-    const FqU v = fqu_sqr(u);
-    const FqU w = fqu_mul(u, v);
-    const FqU s = fqu_mul(a.x, v);
-    const FqU xx = fqu_sqr(a.x);
+    const FqU v = fqu_sqr_s(u);
+    const FqU w = fqu_mul_s(u, v);
+    const FqU s = fqu_mul_s(a.x, v);
+    const FqU xx = fqu_sqr_s(a.x);
     FqU m;
 #pragma unroll
     for (int i = 0; i < 14; i++) m.l[i] = 3u * xx.l[i];                   // M = 3 X1^2, limbs < 2^30, value < 3.03 p
-    const FqU mm = fqu_sqr(m);
+    const FqU mm = fqu_sqr(m);                                            // limbs up to 3 * 2^28: a column can reach 2^62.98, additive
     FqU x3;
 #pragma unroll
     for (int i = 0; i < 14; i++) x3.l[i] = mm.l[i] + (fqu_8p_wide(i) - s.l[i] - s.l[i]);   // M^2 - 2 S + 8 p
@@ -961,9 +1045,9 @@ __device__ __forceinline__ void xyzzu_double(XYZZU& a) {
     FqU nw;
 #pragma unroll
     for (int i = 0; i < 14; i++) nw.l[i] = fqu_8p(i) - w.l[i];            // 8 p - W (lazy)
-    const FqU y3 = fqu_mul_add(m, d, nw, a.y);                            // M (S - X3) - W Y1
-    a.zz = fqu_mul(v, a.zz);
-    a.zzz = fqu_mul(w, a.zzz);
+    const FqU y3 = fqu_mul_add_s(m, d, nw, a.y);                          // M (S - X3) - W Y1
+    a.zz = fqu_mul_s(v, a.zz);
+    a.zzz = fqu_mul_s(w, a.zzz);
     a.x = x3;
     a.y = y3;
 }
@@ -1040,9 +1124,9 @@ FQU_SUBN(fqu_subn_128, fqu_128p)
 
 // (a0 + a1 u)(b0 + b1 u), u^2 = -5: Karatsuba (quadratic_extension.rs:571-583), operands normalised
 __device__ __forceinline__ Fq2U fq2u_mul(const Fq2U& a, const Fq2U& b) {
-    FqU v0 = fqu_mul(a.c0, b.c0);
-    FqU v1 = fqu_mul(a.c1, b.c1);
-    FqU m = fqu_mul(fqu_add_lazy(a.c0, a.c1), fqu_add_lazy(b.c0, b.c1));
+    FqU v0 = fqu_mul_s(a.c0, b.c0);
+    FqU v1 = fqu_mul_s(a.c1, b.c1);
+    FqU m = fqu_mul_s(fqu_add_lazy(a.c0, a.c1), fqu_add_lazy(b.c0, b.c1));   // limbs < 2^29 each: signed columns
     Fq2U r;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
@@ -1062,8 +1146,8 @@ __device__ __forceinline__ Fq2U fq2u_sqr(const Fq2U& a) {
         d2.l[i] = a.c0.l[i] + 5u * a.c1.l[i];
     }
     d2 = fqu_normalize(d2);
-    FqU v = fqu_mul(d1, d2);
-    FqU v2 = fqu_mul(a.c0, a.c1);
+    FqU v = fqu_mul_s(d1, d2);                                            // d2 normalised: signed columns
+    FqU v2 = fqu_mul_s(a.c0, a.c1);
     Fq2U r;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
@@ -1099,8 +1183,8 @@ __device__ __forceinline__ FqU fqu_neg5(const FqU& a) {
 // results are multiply outputs (< 1.01 p + (a0 b0 + a1 n5b1) / 2^392, i.e. < 3 p for the operand values below).
 __device__ __forceinline__ Fq2U fq2u_mul_n5(const Fq2U& a, const Fq2U& b, const FqU& n5b1) {
     Fq2U r;
-    r.c0 = fqu_mul_add(a.c0, b.c0, a.c1, n5b1);
-    r.c1 = fqu_mul_add(a.c0, b.c1, a.c1, b.c0);
+    r.c0 = fqu_mul_add_s(a.c0, b.c0, a.c1, n5b1);                         // 28 products below 2^56: signed columns
+    r.c1 = fqu_mul_add_s(a.c0, b.c1, a.c1, b.c0);
     return r;
 }
 __device__ __forceinline__ bool fqu_low_in(const FqU& a, u32 lo, u32 hi) { return (a.l[0] - lo) <= (hi - lo); }
@@ -1119,7 +1203,7 @@ __device__ __forceinline__ bool fq2u_xyzz_acc_mixed(Fq2U& ax, Fq2U& ay, Fq2U& az
         e0.l[i] = fqu_128p(i) - ax.c0.l[i];              // 128 p - X1, limb-wise non-negative (X1 normalised)
         e1.l[i] = fqu_128p(i) - ax.c1.l[i];
     }
-    Fq2U pp{fqu_mul_add_hi(qx.c0, azz.c0, qx.c1, n5zz, e0), fqu_mul_add_hi(qx.c0, azz.c1, qx.c1, azz.c0, e1)};   // H = U2 - X1 + 128 p
+    Fq2U pp{fqu_mul_add_hi_s(qx.c0, azz.c0, qx.c1, n5zz, e0), fqu_mul_add_hi_s(qx.c0, azz.c1, qx.c1, azz.c0, e1)};   // H = U2 - X1 + 128 p
     if (fqu_low_in(pp.c0, 40, 150) && fqu_low_in(pp.c1, 40, 150)) return false;
     const FqU n5zzz = fqu_neg5<false>(azzz.c1);
     FqU nay0, nay1;                                      // 64 p - Y1 (Y1 < 36 p), lazy: r's addend here, a factor of Y3 below
@@ -1128,7 +1212,7 @@ __device__ __forceinline__ bool fq2u_xyzz_acc_mixed(Fq2U& ax, Fq2U& ay, Fq2U& az
         nay0.l[i] = fqu_64p(i) - ay.c0.l[i];
         nay1.l[i] = fqu_64p(i) - ay.c1.l[i];
     }
-    Fq2U r{fqu_mul_add_hi(qy.c0, azzz.c0, qy.c1, n5zzz, nay0), fqu_mul_add_hi(qy.c0, azzz.c1, qy.c1, azzz.c0, nay1)};   // r = S2 - Y1 + 64 p
+    Fq2U r{fqu_mul_add_hi_s(qy.c0, azzz.c0, qy.c1, n5zzz, nay0), fqu_mul_add_hi_s(qy.c0, azzz.c1, qy.c1, azzz.c0, nay1)};   // r = S2 - Y1 + 64 p
     Fq2U p2 = fq2u_sqr(pp);                              // c1 = 2 v2 < 3 p
     const FqU n5p2 = fqu_neg5<false>(p2.c1);
     azz = fq2u_mul_n5(p2, azz, n5zz);
@@ -1143,13 +1227,13 @@ __device__ __forceinline__ bool fq2u_xyzz_acc_mixed(Fq2U& ax, Fq2U& ay, Fq2U& az
             d2.l[i] = r.c0.l[i] + 5u * r.c1.l[i];
         }
         d2 = fqu_normalize(d2);
-        const FqU v2 = fqu_mul(r.c0, r.c1);
+        const FqU v2 = fqu_mul_s(r.c0, r.c1);
 #pragma unroll
         for (int i = 0; i < 14; i++) {
             e0.l[i] = (fqu_16p_u4(i) - 4u * v2.l[i]) + (fqu_64p_u3(i) - p3.c0.l[i] - qv.c0.l[i] - qv.c0.l[i]);   // < 2^31.3
             e1.l[i] = (v2.l[i] + v2.l[i]) + (fqu_64p_u3(i) - p3.c1.l[i] - qv.c1.l[i] - qv.c1.l[i]);
         }
-        ax.c0 = fqu_mul_hi(d1, d2, e0);
+        ax.c0 = fqu_mul_hi_s(d1, d2, e0);
         ax.c1 = fqu_normalize(e1);
     }
 #else                      // -DCZK_G2_KARATSUBA: Karatsuba products (fq2u_mul_k): 952 instead of 1148 multiply-adds each, outputs < 2.1 p
@@ -1182,8 +1266,8 @@ __device__ __forceinline__ bool fq2u_xyzz_acc_mixed(Fq2U& ax, Fq2U& ay, Fq2U& az
     // Y3 = d r - Y1 PPP, each component four products under one reduction (operands: d, r, p3 normalised; -Y1 lazy)
     const FqU n5r = fqu_neg5<true>(r.c1);
     const FqU n5p3 = fqu_neg5<false>(p3.c1);
-    ay.c0 = fqu_mul_add4(d.c0, r.c0, d.c1, n5r, nay0, p3.c0, nay1, n5p3);
-    ay.c1 = fqu_mul_add4(d.c0, r.c1, d.c1, r.c0, nay0, p3.c1, nay1, p3.c0);
+    ay.c0 = fqu_mul_add4_s(d.c0, r.c0, d.c1, n5r, nay0, p3.c0, nay1, n5p3);
+    ay.c1 = fqu_mul_add4_s(d.c0, r.c1, d.c1, r.c0, nay0, p3.c1, nay1, p3.c0);
     return true;
 }
 

@@ -62,6 +62,13 @@ enum czk_lab_arith_op {
     CZK_PROBE_XYZZU2_ADD = 51,            // a + inf, b + inf : 226 -> 112 + inf
     CZK_PROBE_XYZZU2_DOUBLE = 52,         // a + inf : 113 -> 112 + inf
     CZK_PROBE_XYZZU2_ACC_MIXED = 53,      // ax, ay, azz, azzz, qx, qy : 168 -> 112 + returned bool
+    // fqu.h: the signed-column (`_s`) forms of the multiplies; operands as above, within the signed-column contract
+    CZK_PROBE_FQU_MUL_S = 70,             // a, b : 28 -> 14
+    CZK_PROBE_FQU_SQR_S = 71,             // a : 14 -> 14
+    CZK_PROBE_FQU_MUL_ADD_S = 72,         // a, b, c, d : 56 -> 14
+    CZK_PROBE_FQU_MUL_ADD_HI_S = 73,      // a, b, c, d, e : 70 -> 14
+    CZK_PROBE_FQU_MUL_HI_S = 74,          // a, b, e : 42 -> 14
+    CZK_PROBE_FQU_MUL_ADD4_S = 75,        // a .. h : 112 -> 14
     // fru.h
     CZK_PROBE_FRU_MUL = 60,               // a, b : 18 -> 9
     CZK_PROBE_FRU_NORMALIZE = 62,         // 9 -> 9

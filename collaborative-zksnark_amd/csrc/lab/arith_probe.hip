@@ -95,6 +95,13 @@ PROBE(PFquMulAddHi, 70, 14, stq(o, fqu_mul_add_hi(ldq(i), ldq(i + 14), ldq(i + 2
 PROBE(PFquMulHi, 42, 14, stq(o, fqu_mul_hi(ldq(i), ldq(i + 14), ldq(i + 28)));)
 PROBE(PFquMulAdd4, 112, 14,
       stq(o, fqu_mul_add4(ldq(i), ldq(i + 14), ldq(i + 28), ldq(i + 42), ldq(i + 56), ldq(i + 70), ldq(i + 84), ldq(i + 98)));)
+PROBE(PFquMulS, 28, 14, stq(o, fqu_mul_s(ldq(i), ldq(i + 14)));)
+PROBE(PFquSqrS, 14, 14, stq(o, fqu_sqr_s(ldq(i)));)
+PROBE(PFquMulAddS, 56, 14, stq(o, fqu_mul_add_s(ldq(i), ldq(i + 14), ldq(i + 28), ldq(i + 42)));)
+PROBE(PFquMulAddHiS, 70, 14, stq(o, fqu_mul_add_hi_s(ldq(i), ldq(i + 14), ldq(i + 28), ldq(i + 42), ldq(i + 56)));)
+PROBE(PFquMulHiS, 42, 14, stq(o, fqu_mul_hi_s(ldq(i), ldq(i + 14), ldq(i + 28)));)
+PROBE(PFquMulAdd4S, 112, 14,
+      stq(o, fqu_mul_add4_s(ldq(i), ldq(i + 14), ldq(i + 28), ldq(i + 42), ldq(i + 56), ldq(i + 70), ldq(i + 84), ldq(i + 98)));)
 PROBE(PFquNormalize, 14, 14, stq(o, fqu_normalize(ldq(i)));)
 PROBE(PFquSubLazy4, 28, 14, stq(o, fqu_sub_lazy<4>(ldq(i), ldq(i + 14)));)
 PROBE(PFquSubLazy8, 28, 14, stq(o, fqu_sub_lazy<8>(ldq(i), ldq(i + 14)));)
@@ -209,6 +216,12 @@ extern "C" int czk_lab_arith_probe(czk_ctx* ctx, int op, const uint32_t* in, siz
     case CZK_PROBE_FQU_MUL_ADD_HI: RUN(PFquMulAddHi);
     case CZK_PROBE_FQU_MUL_HI: RUN(PFquMulHi);
     case CZK_PROBE_FQU_MUL_ADD4: RUN(PFquMulAdd4);
+    case CZK_PROBE_FQU_MUL_S: RUN(PFquMulS);
+    case CZK_PROBE_FQU_SQR_S: RUN(PFquSqrS);
+    case CZK_PROBE_FQU_MUL_ADD_S: RUN(PFquMulAddS);
+    case CZK_PROBE_FQU_MUL_ADD_HI_S: RUN(PFquMulAddHiS);
+    case CZK_PROBE_FQU_MUL_HI_S: RUN(PFquMulHiS);
+    case CZK_PROBE_FQU_MUL_ADD4_S: RUN(PFquMulAdd4S);
     case CZK_PROBE_FQU_NORMALIZE: RUN(PFquNormalize);
     case CZK_PROBE_FQU_SUB_LAZY_4: RUN(PFquSubLazy4);
     case CZK_PROBE_FQU_SUB_LAZY_8: RUN(PFquSubLazy8);

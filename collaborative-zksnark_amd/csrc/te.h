@@ -54,19 +54,21 @@ __device__ __forceinline__ void teu_store(u64* p, const TEU& a) {
     fp_store<FqParams>(p + 18, fqu_pack(a.t));
 }
 
-// the four output products shared by every formula below: (E, F, G, H) -> (E F, G H, F G, E H); operands lazy (limbs < 2^30)
+// the four output products of the additions below: (E, F, G, H) -> (E F, G H, F G, E H); operands lazy (limbs < 2^30).  There
+// E = B - A + 4 p and F = D - C + 4 p carry a K p table (limbs up to 2^29.5 and 2^29.9), G = D + C and H = B + A do not (< 2^29.6, < 2^29):
+// G H and E H fit signed columns (fqu_mul_s), E F and F G do not (a column can reach 2^63.3) and keep the additive loop.
 __device__ __forceinline__ void teu_finish(TEU& a, const FqU& E, const FqU& F, const FqU& G, const FqU& H) {
     a.x = fqu_mul(E, F);
-    a.y = fqu_mul(G, H);
+    a.y = fqu_mul_s(G, H);
     a.z = fqu_mul(F, G);
-    a.t = fqu_mul(E, H);
+    a.t = fqu_mul_s(E, H);
 }
 // a += (ym, yp, k2) = (Y2 - X2, Y2 + X2, 2 D X2 Y2) of an affine table point; madd-2008-hwcd-3, 7M.  ym, yp canonical (< p);
 // k2 canonical or the lazy 4 p - k2 of a negated point (limbs < 2^30).
 __device__ __forceinline__ void teu_madd(TEU& a, const FqU& ym, const FqU& yp, const FqU& k2) {
-    const FqU A = fqu_mul(fqu_sub_lazy<8>(a.y, a.x), ym);   // (Y1 - X1 + 8 p)(Y2 - X2)   (X1 < 5 p after teu_from_niels)
-    const FqU B = fqu_mul(fqu_add_lazy(a.y, a.x), yp);      // (Y1 + X1)(Y2 + X2)
-    const FqU C = fqu_mul(a.t, k2);                         // T1 2 D T2
+    const FqU A = fqu_mul_s(fqu_sub_lazy<8>(a.y, a.x), ym);   // (Y1 - X1 + 8 p)(Y2 - X2)   (X1 < 5 p after teu_from_niels)
+    const FqU B = fqu_mul_s(fqu_add_lazy(a.y, a.x), yp);      // (Y1 + X1)(Y2 + X2)
+    const FqU C = fqu_mul_s(a.t, k2);                         // T1 2 D T2   (one factor of each normalised: signed columns)
     FqU F, G;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
@@ -109,10 +111,10 @@ __device__ __forceinline__ void teu_madd_il(TEU& a, const FqU& ym, const FqU& yp
 #endif
 // a += b, both extended (add-2008-hwcd-3, 8M + one multiplication by the constant 2 D)
 __device__ __forceinline__ void teu_add(TEU& a, const TEU& b) {
-    const FqU A = fqu_mul(fqu_sub_lazy<8>(a.y, a.x), fqu_sub_lazy<8>(b.y, b.x));
-    const FqU B = fqu_mul(fqu_add_lazy(a.y, a.x), fqu_add_lazy(b.y, b.x));
-    const FqU C = fqu_mul(fqu_mul(a.t, b.t), te_2d_u());
-    const FqU Dh = fqu_mul(a.z, b.z);
+    const FqU A = fqu_mul(fqu_sub_lazy<8>(a.y, a.x), fqu_sub_lazy<8>(b.y, b.x));   // both factors carry 8 p (limbs < 2^29.6): a column can reach 2^62.9, additive
+    const FqU B = fqu_mul_s(fqu_add_lazy(a.y, a.x), fqu_add_lazy(b.y, b.x));
+    const FqU C = fqu_mul_s(fqu_mul_s(a.t, b.t), te_2d_u());
+    const FqU Dh = fqu_mul_s(a.z, b.z);
     FqU F, G;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
@@ -125,15 +127,15 @@ __device__ __forceinline__ void teu_add(TEU& a, const TEU& b) {
 // kT = 2 D T of a point that is an operand of more than one addition (the running sum of the bucket reduction: addend of A += running and
 // accumulator of the next running += P), computed once.  t: a multiply output or a loaded coordinate (normalised), 2 D canonical: kT is
 // a multiply output, < 1.01 p, normalised.
-__device__ __forceinline__ FqU teu_kt(const TEU& b) { return fqu_mul(b.t, te_2d_u()); }
+__device__ __forceinline__ FqU teu_kt(const TEU& b) { return fqu_mul_s(b.t, te_2d_u()); }
 // a += b with kTb = teu_kt(b): teu_add with C = T1 (2 D T2) instead of (T1 T2) 2 D, 8M.  Both factors of C are normalised (a.t: a
 // multiply output or a loaded coordinate; kTb: a multiply output), so C is a multiply output below 1.01 p exactly as in teu_add, and
 // F = D - C + 4 p, G = D + C keep their bounds (limbs < 2^30).  The same residue as teu_add's C, not always the same representative.
 __device__ __forceinline__ void teu_add_kt(TEU& a, const TEU& b, const FqU& kTb) {
-    const FqU A = fqu_mul(fqu_sub_lazy<8>(a.y, a.x), fqu_sub_lazy<8>(b.y, b.x));
-    const FqU B = fqu_mul(fqu_add_lazy(a.y, a.x), fqu_add_lazy(b.y, b.x));
-    const FqU C = fqu_mul(a.t, kTb);
-    const FqU Dh = fqu_mul(a.z, b.z);
+    const FqU A = fqu_mul(fqu_sub_lazy<8>(a.y, a.x), fqu_sub_lazy<8>(b.y, b.x));   // additive, as in teu_add
+    const FqU B = fqu_mul_s(fqu_add_lazy(a.y, a.x), fqu_add_lazy(b.y, b.x));
+    const FqU C = fqu_mul_s(a.t, kTb);
+    const FqU Dh = fqu_mul_s(a.z, b.z);
     FqU F, G;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
@@ -145,8 +147,8 @@ __device__ __forceinline__ void teu_add_kt(TEU& a, const TEU& b, const FqU& kTb)
 }
 // a = 2 a (dbl-2008-hwcd with a = -1: 4M + 4S)
 __device__ __forceinline__ void teu_double(TEU& a) {
-    const FqU A = fqu_sqr(a.x), B = fqu_sqr(a.y), Cz = fqu_sqr(a.z);
-    const FqU S = fqu_sqr(fqu_add_lazy(a.x, a.y));
+    const FqU A = fqu_sqr_s(a.x), B = fqu_sqr_s(a.y), Cz = fqu_sqr_s(a.z);
+    const FqU S = fqu_sqr_s(fqu_add_lazy(a.x, a.y));
     const FqU G = fqu_normalize(fqu_sub_lazy<4>(B, A));     // G = B - A + 4 p, normalised so that F below stays under 2^30 per limb
     FqU E, F, H;
 #pragma unroll
@@ -155,7 +157,12 @@ __device__ __forceinline__ void teu_double(TEU& a) {
         F.l[i] = G.l[i] + (fqu_8p_u2(i) - Cz.l[i] - Cz.l[i]);           // G - 2 Z^2 + 8 p
         H.l[i] = fqu_8p_u2(i) - A.l[i] - B.l[i];                        // -A - B + 8 p
     }
-    teu_finish(a, E, F, G, H);
+    // here G is normalised and E, H carry 8 p: G H and F G fit signed columns, E F (2^63.7) and E H (2^63.3) do not
+    const FqU x = fqu_mul(E, F), y = fqu_mul_s(G, H), z = fqu_mul_s(F, G), t = fqu_mul(E, H);
+    a.x = x;
+    a.y = y;
+    a.z = z;
+    a.t = t;
 }
 
 // (X : Y : Z : T) -> the reference's Jacobian triple of the corresponding point of E, without an inversion:
@@ -223,7 +230,7 @@ __device__ __forceinline__ TEU teu_from_niels(const FqU& ym, const FqU& yp, cons
     a.x = fqu_normalize(fqu_sub_lazy<4>(yp, ym));
     a.y = fqu_normalize(fqu_add_lazy(yp, ym));
     a.z = fqu_normalize(fqu_add_lazy(fqu_one(), fqu_one()));
-    a.t = fqu_mul(k2, fqu_const(idm));
+    a.t = fqu_mul_s(k2, fqu_const(idm));
     return a;
 }
 
