@@ -45,6 +45,9 @@ def _share_material_counts(L, op: int, n: int):
     return t.value, p.value
 
 
+CZK_GSZ_OP_MUL, CZK_GSZ_OP_INV, CZK_GSZ_OP_PARTIAL_PRODUCTS, CZK_GSZ_OP_PRODUCT_CHECK = 0, 1, 2, 3   # czk_gsz_material_counts
+
+
 def open_commit_flags(commit) -> int:
     """commit = True | False | "tree" -> the flags of czk_spdz_batch_open"""
     if isinstance(commit, str):
@@ -537,6 +540,40 @@ class Context:
     def share_partial_products(self, lpp: int, parties: int, mac_shares, x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr, out_ptr, n: int):
         """czk_share_partial_products -> (failed MAC checks, zero divisors)"""
         return self._share_call(self._L.czk_share_partial_products, lpp, parties, mac_shares, (x_ptr, pb_ptr, pc_ptr, tx_ptr, ty_ptr, tz_ptr), out_ptr, n)
+
+    # ---- gsz20's batch_mult / batch_inv / partial_products and the product check on device lanes (czk.h; csrc/gsz_mul.hip) -------------
+    def gsz_material_counts(self, op: int, n: int):
+        """(double shares, random shares) one call of `op` (CZK_GSZ_OP_*) over n elements consumes"""
+        d, r = C.c_size_t(0), C.c_size_t(0)
+        rc = self._L.czk_gsz_material_counts(C.c_int(op), C.c_size_t(n), C.byref(d), C.byref(r))
+        if rc:
+            raise CzkError(rc, "czk_gsz_material_counts: unknown op or a count that overflows")
+        return d.value, r.value
+
+    def _gsz_call(self, fn, parties, degree, ptrs, n):
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        out = ptrs[-1]
+        self._ck(fn(self._h, C.c_size_t(parties), C.c_uint(degree), *[_ptr(p) for p in ptrs[:-1]], _ptr(out), C.c_size_t(n), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def gsz_share_batch_mul(self, parties: int, degree: int, x_ptr, y_ptr, doubles_r_ptr, doubles_r2_ptr, out_ptr, n: int):
+        """czk_gsz_share_batch_mul: every vector `parties` device lanes, party j's lane = p(w^j) -> (degree violations, 0)"""
+        return self._gsz_call(self._L.czk_gsz_share_batch_mul, parties, degree, (x_ptr, y_ptr, doubles_r_ptr, doubles_r2_ptr, out_ptr), n)
+
+    def gsz_share_batch_inv(self, parties: int, degree: int, x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr, n: int):
+        """czk_gsz_share_batch_inv -> (degree violations, zero divisors)"""
+        return self._gsz_call(self._L.czk_gsz_share_batch_inv, parties, degree, (x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr), n)
+
+    def gsz_share_partial_products(self, parties: int, degree: int, x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr, n: int):
+        """czk_gsz_share_partial_products -> (degree violations, zero divisors)"""
+        return self._gsz_call(self._L.czk_gsz_share_partial_products, parties, degree, (x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr), n)
+
+    def gsz_product_check(self, parties: int, degree: int, xs_ptr, ys_ptr, zs_ptr, n: int, doubles_r_ptr, doubles_r2_ptr, rands_ptr):
+        """czk_gsz_product_check over n triples -> (ok, degree violations); ok = False is a result, not an error"""
+        ok, bad = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.czk_gsz_product_check(self._h, C.c_size_t(parties), C.c_uint(degree), _ptr(xs_ptr), _ptr(ys_ptr), _ptr(zs_ptr), C.c_size_t(n),
+                                             _ptr(doubles_r_ptr), _ptr(doubles_r2_ptr), _ptr(rands_ptr), C.byref(ok), C.byref(bad)))
+        return bool(ok.value), bad.value
 
     def share_domain_constants(self, parties: int):
         out = np.zeros((3, 4), dtype=np.uint64)

@@ -191,6 +191,7 @@ struct czk_ctx {
     czk::DeviceBuf ntt_scratch;   // one lane-batch for the out-of-place NTT passes
     czk::DeviceBuf poly_scratch;  // segment sums of czk_poly_div_linear (poly.hip)
     czk::DeviceBuf share_tab;     // size_inv * w^(-jk) table of czk_fr_gsz_open (share.hip)
+    std::vector<uint64_t> share_tab_host;   // its host copy, the source of the upload (share.hip gsz_open_table)
     czk::DeviceBuf sqrt_tab;      // 2-adic discrete-log tables of the Fq square root (point_codec.hip), built on first use
     int num_cu = 256;
     size_t lds_per_block = 64 * 1024;   // hipDeviceProp_t::sharedMemPerBlock (gfx950: 160 KiB)
@@ -366,6 +367,8 @@ int share_combine_launch(czk_ctx* ctx, unsigned lpp, bool king, const Fr& mac_sh
                          size_t out_stride, size_t n);
 // out_l[i] = c_l[i] * (k[i] * prefix[i]) (prefix null: c_l[i] * k[i]); k[i] == 0 (czk_fr_batch_inverse kept a zero) adds one to ctx->share_cnt[1]
 int share_scale_launch(czk_ctx* ctx, unsigned lanes, ShareVec c, const u64* k, const u64* prefix, u64* out, size_t out_stride, size_t n);
+// implemented in share.hip: builds and uploads ctx->share_tab for `parties` (stream order); CZK_ERR_SIZE when the share domain does not exist
+int gsz_open_table(czk_ctx* ctx, size_t parties);
 // implemented in ntt.hip
 // `addend` (lanes x D canonical Fr, not the lanes being transformed) rides on the last pass's store: a coset inverse transform writes
 // (coset_ifft(data) - addend) * *scale, a forward or coset forward transform writes its output + addend (scale unused).  Same values as the pointwise kernels.

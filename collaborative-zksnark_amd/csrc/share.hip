@@ -138,9 +138,24 @@ extern "C" int czk_fr_gsz_open(czk_ctx* ctx, const uint64_t* shares, size_t part
     CZK_TRY(czk_share_domain_constants(ctx, parties, dom));
     if (!n) return CZK_OK;
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    // size_inv * w^(-j k) for j, k < parties (host arithmetic: at most 96^2 multiplies)
+    CZK_TRY(gsz_open_table(ctx, parties));
+    if (!ctx->open_bad) CZK_HIP(ctx, hipMalloc(&ctx->open_bad, 8));
+    CZK_HIP(ctx, hipMemsetAsync(ctx->open_bad, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_gsz_open, dim3(share_grid(ctx, n)), dim3(256), 0, ctx->stream, (const u64*)shares, parties, n, (const u64*)ctx->share_tab.p, degrees, degree,
+                       (u64*)out_value, ctx->open_bad);
+    CZK_HIP(ctx, hipGetLastError());
+    return count_readback(ctx, out_bad);
+}
+
+// ctx->share_tab = size_inv * w^(-j k) for j, k < parties, enqueued on the context's stream.  The host copy lives in the context, so it outlasts the
+// copy whatever the caller does next.
+int czk::gsz_open_table(czk_ctx* ctx, size_t parties) {
+    u64 dom[12];
+    CZK_TRY(czk_share_domain_constants(ctx, parties, dom));
+    // host arithmetic: at most 96^2 multiplies
     const Fr size_inv = host_fr(dom), winv = host_fr(dom + 8);
-    std::vector<u64> tab(4 * parties * parties);
+    std::vector<u64>& tab = ctx->share_tab_host;
+    tab.resize(4 * parties * parties);
     Fr wj = Fr::one();                                    // w^-j
     for (size_t j = 0; j < parties; j++) {
         Fr e = size_inv;                                  // size_inv * w^(-j k)
@@ -152,10 +167,5 @@ extern "C" int czk_fr_gsz_open(czk_ctx* ctx, const uint64_t* shares, size_t part
     }
     CZK_TRY(ensure_buf(ctx, ctx->share_tab, tab.size() * 8));
     CZK_HIP(ctx, hipMemcpyAsync(ctx->share_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (!ctx->open_bad) CZK_HIP(ctx, hipMalloc(&ctx->open_bad, 8));
-    CZK_HIP(ctx, hipMemsetAsync(ctx->open_bad, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_gsz_open, dim3(share_grid(ctx, n)), dim3(256), 0, ctx->stream, (const u64*)shares, parties, n, (const u64*)ctx->share_tab.p, degrees, degree,
-                       (u64*)out_value, ctx->open_bad);
-    CZK_HIP(ctx, hipGetLastError());
-    return count_readback(ctx, out_bad);   // also orders the staging vector's lifetime: the copy has completed
+    return CZK_OK;
 }

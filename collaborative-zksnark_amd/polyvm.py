@@ -16,7 +16,10 @@ product, right for the reference's king_share stand-in sharing alone, where ever
 `GpuBackend(..., sharing=Sharing(lpp, parties, source))` the lanes are a real additive or SPDZ sharing and `mul`, `inverse` and
 `prefix_product` of shared arrays are FieldShare::batch_mul / batch_inv / partial_products (czk_share_*, include/czk.h) on correlated randomness
 from `source`; `open_shared_proof` is the parties' last step.  The `lift` tuple keeps its 0 / 1 meaning, so under `sharing` the MAC key is the
-reference's 0 / 1 key (the king's share is one, share/spdz.rs:30-37); the C calls take any key.
+reference's 0 / 1 key (the king's share is one, share/spdz.rs:30-37); the C calls take any key.  `Sharing(1, parties, source, scheme="gsz")`
+makes the lanes a real degree-t Shamir sharing (one lane per party, p(w^j) on lane j): `mul`, `inverse` and `prefix_product` are gsz20's batch_mult /
+batch_inv / partial_products (czk_gsz_share_*), every `mul` queues its triple, and `transcript_point` / `open_shared_proof` run gsz20's product check
+(czk_gsz_product_check) over the queue before anything is opened.
 """
 from __future__ import annotations
 
@@ -239,17 +242,33 @@ class Backend:
 
 
 class SharingError(RuntimeError):
-    """a MAC check failed, or a shared value that had to be inverted opened to zero (the reference asserts / unwraps there)"""
+    """a MAC check, a degree bound or GSZ's product check failed, or a shared value that had to be inverted opened to zero (the reference asserts /
+    unwraps there)"""
 
 
 class Sharing:
     """The lanes of a GpuBackend as a real sharing: lpp = 1 additive, lpp = 2 SPDZ (lane lpp p = party p's sh, lane lpp p + 1 its mac), `parties`
-    parties, correlated randomness from `source` (DummySource, SeededDealer).  MAC key: the reference's 0 / 1 key (see the module's head)."""
+    parties, correlated randomness from `source` (DummySource, SeededDealer).  MAC key: the reference's 0 / 1 key (see the module's head).
+    scheme="gsz" (lpp = 1): lane j is party j's Shamir share p(w^j) of degree t = (parties - 1) // 2 (gsz20/mod.rs:94-105); a public value lifts to
+    every lane (from_public, :185-187: a degree-0 sharing); `parties` must be a size the share domain exists for (2^a or 3 * 2^a, at most 96)."""
 
-    def __init__(self, lpp: int, parties: int, source, rank: int | None = None):
+    def __init__(self, lpp: int, parties: int, source, rank: int | None = None, scheme: str | None = None):
         """rank=None: all parties' lanes on one backend (lpp * parties lanes).  rank=r: one process per party -- the backend holds party r's lpp
         lanes and the protocols run over the czk_net communicator given to parallel.use_net (the CZK_NET_SHM transport is the tested one); every
         party's source must deal the same material (the same seed), of which it keeps its own lanes."""
+        self.scheme = scheme or ("spdz" if lpp == 2 else "additive")
+        if self.scheme == "gsz":
+            odd = parties // 3 if parties > 0 and parties % 3 == 0 else parties
+            if lpp != 1 or not 1 <= parties <= 96 or odd & (odd - 1):
+                raise ValueError("Sharing(scheme='gsz'): one lane per party, parties = 2^a or 3 * 2^a, at most 96")
+            if rank is not None:
+                raise ValueError("not built")                                          # GSZ with one process per party
+            self.lpp, self.parties, self.lanes, self.source, self.rank = 1, parties, parties, source, None
+            self.degree = (parties - 1) // 2
+            self.lift, self.mac_shares, self.backend_lanes = tuple([1] * parties), None, parties
+            return
+        if self.scheme != ("spdz" if lpp == 2 else "additive"):
+            raise ValueError(f"Sharing: scheme {scheme!r} does not go with lpp = {lpp}")
         if lpp not in (1, 2) or not 1 <= parties <= 32 or (rank is not None and not 0 <= rank < parties):
             raise ValueError("Sharing: lpp is 1 (additive) or 2 (SPDZ), 1 to 32 parties, rank below parties")
         if rank is not None and lpp == 1:
@@ -285,6 +304,14 @@ class DummySource:
     def inv_pairs(self, B, n: int, inverses: int = 0):
         one = self._one(B, n)
         return one, one
+
+    # GSZ: the reference's stubs rand / double_rand (gsz20/mod.rs:383-406) hand every party a one
+    def doubles(self, B, n: int):
+        one = self._one(B, n)
+        return one, one
+
+    def rands(self, B, n: int):
+        return self._one(B, n)
 
 
 class SeededDealer:
@@ -325,6 +352,27 @@ class SeededDealer:
         if inverses:
             c = B.concat([B.resized(B.inverse(b), inverses), B.drop_first(b, inverses)]) if inverses < n else B.inverse(b)
         return self._split(B, b), self._split(B, c)
+
+    def _shamir(self, B, v, deg: int):
+        """public (1, n, 4) -> a random degree-`deg` Shamir sharing on the share domain: lane j = v + sum_k c_k w^(j k), c_k random"""
+        S, n = B.sharing, B.length(v)
+        w = unmont(B.ctx.share_domain_constants(S.parties)["group_gen"])
+        cs = [self._random(B, n) for _ in range(deg)]
+        lanes = []
+        for j in range(S.parties):
+            acc = v
+            for k, c in enumerate(cs, 1):
+                acc = B.add(acc, B.scale(c, pow(w, j * k, R_MOD)))
+            lanes.append(acc)
+        return B.lane_stack(lanes)
+
+    def doubles(self, B, n: int):
+        """n double shares (gsz20/mod.rs:395-406): one random value under a polynomial of degree t and under one of degree 2 t"""
+        v, t = self._random(B, n), B.sharing.degree
+        return self._shamir(B, v, t), self._shamir(B, v, 2 * t)
+
+    def rands(self, B, n: int):
+        return self._shamir(B, self._random(B, n), B.sharing.degree)
 
 
 def shared_stream_context(czk, device: int = 0):
@@ -389,6 +437,9 @@ class GpuBackend(Backend):
         self.opener = None      # party-per-rank layouts: callable(backend, (k, lanes, 4) device tensor) -> opened values, run over torch.distributed
         self.opened = []        # what the opener returned, in order
         self.msm_points = 0
+        self._gsz_queue = []    # scheme "gsz": the (x, y, z) of every mul since the last product check (gsz20's add_types)
+        self.gsz_queue_peak = 0     # most triples one check has covered; each holds 3 * parties * 32 bytes of device memory until then
+        self.gsz_checks = 0
 
     M = 1   # CZK_MEM_DEVICE
     commit_opens = True   # Sharing(rank=...): the flags of the protocols' opens -- True, False or "tree" (binding.open_commit_flags)
@@ -542,6 +593,8 @@ class GpuBackend(Backend):
         assert a.shape[0] == S.backend_lanes and (b is None or b.shape == a.shape), (what, a.shape, None if b is None else b.shape)
         if not n:
             return self._new(S.backend_lanes, n)
+        if S.scheme == "gsz":
+            return self._gsz_call(what, a, b)
         op = {"batch_mul": self.czk.binding.CZK_SHARE_OP_MUL, "batch_inv": self.czk.binding.CZK_SHARE_OP_INV,
               "partial_products": self.czk.binding.CZK_SHARE_OP_PARTIAL_PRODUCTS}[what]
         n_triples, n_pairs = self.ctx.share_material_counts(op, n)
@@ -569,6 +622,44 @@ class GpuBackend(Backend):
         if bad or zero:
             raise SharingError(f"{what} of {n} shared elements: {bad} failed MAC check(s), {zero} zero divisor(s)")
         return out
+
+    def _gsz_call(self, what, a, b=None):
+        """gsz20's batch_mult / batch_inv / partial_products of Shamir-shared arrays: one C call on double and random shares from the source.  A mul
+        queues its triple for the product check; the products inside batch_inv and partial_products are opened where they are made and never exist
+        as lanes, so they are not queued (the reference queues them too)."""
+        S, n, bd = self.sharing, a.shape[1], self.czk.binding
+        op = {"batch_mul": bd.CZK_GSZ_OP_MUL, "batch_inv": bd.CZK_GSZ_OP_INV, "partial_products": bd.CZK_GSZ_OP_PARTIAL_PRODUCTS}[what]
+        nd, nr = self.ctx.gsz_material_counts(op, n)
+        dr, dr2 = S.source.doubles(self, nd)
+        out = self._new(S.lanes, n)
+        if what == "batch_mul":
+            b = b.contiguous()
+            bad, zero = self.ctx.gsz_share_batch_mul(S.parties, S.degree, a.data_ptr(), b.data_ptr(), dr.data_ptr(), dr2.data_ptr(), out.data_ptr(), n)
+            self._gsz_queue.append((a, b, out))
+        else:
+            rands = S.source.rands(self, nr)
+            fn = self.ctx.gsz_share_batch_inv if what == "batch_inv" else self.ctx.gsz_share_partial_products
+            bad, zero = fn(S.parties, S.degree, a.data_ptr(), dr.data_ptr(), dr2.data_ptr(), rands.data_ptr(), out.data_ptr(), n)
+        if bad or zero:
+            raise SharingError(f"{what} of {n} shared elements: {bad} degree violation(s), {zero} zero divisor(s)")
+        return out
+
+    def gsz_check(self):
+        """check_accumulated_field_products (gsz20/mod.rs:412-431): gsz20's product check over every triple queued since the last one, as ONE call on
+        the concatenated queue.  Runs before anything is opened (transcript_point, open_shared_proof).  SharingError when it fails."""
+        if not self._gsz_queue:
+            return
+        S, q = self.sharing, self._gsz_queue
+        self._gsz_queue = []
+        xs, ys, zs = (q[0][k] if len(q) == 1 else self.torch.cat([t[k] for t in q], dim=1).contiguous() for k in range(3))
+        n = xs.shape[1]
+        self.gsz_queue_peak, self.gsz_checks = max(self.gsz_queue_peak, n), self.gsz_checks + 1
+        nd, nr = self.ctx.gsz_material_counts(self.czk.binding.CZK_GSZ_OP_PRODUCT_CHECK, n)
+        dr, dr2 = S.source.doubles(self, nd)
+        rands = S.source.rands(self, nr)
+        ok, bad = self.ctx.gsz_product_check(S.parties, S.degree, xs.data_ptr(), ys.data_ptr(), zs.data_ptr(), n, dr.data_ptr(), dr2.data_ptr(), rands.data_ptr())
+        if bad or not ok:
+            raise SharingError(f"product check over {n} triples: {'failed' if not ok else 'passed'}, {bad} degree violation(s)")
 
     def scale(self, a, k):
         out = self._new(a.shape[0], a.shape[1])
@@ -731,6 +822,8 @@ class GpuBackend(Backend):
         return {"value": v, "point": x, "_wit": wit}
 
     def transcript_point(self):
+        if self._gsz_queue:
+            self.gsz_check()                 # open() checks the accumulated products first (gsz20/mod.rs:434-436)
         if not self._pending:
             if self._vals_at:
                 self.ctx.sync()              # slots handed out for blocking reads (div_linear) may still be in flight
@@ -792,6 +885,8 @@ def open_shared_proof(B: Backend, out: dict) -> dict:
     S = B.sharing
     if S is None or S.rank is not None:
         raise ValueError("open_shared_proof needs a backend that holds every party's lanes (sharing=Sharing(...) without rank)")
+    if S.scheme == "gsz":
+        return _open_gsz_proof(B, out)
     sh, mac = list(range(0, S.lanes, S.lpp)), list(range(1, S.lanes, S.lpp)) if S.lpp == 2 else []
     g1 = B.czk.CZK_G1
 
@@ -823,6 +918,50 @@ def open_shared_proof(B: Backend, out: dict) -> dict:
         if isinstance(x, (list, tuple)):
             return type(x)(walk(v, label) for v in x)
         if isinstance(x, np.ndarray) and x.shape == (S.lanes, 4):                  # an evaluation outside an opening (Marlin's evals_*, random_v)
+            return value(x, label)
+        return x
+    return walk(out, "proof")
+
+
+def _open_gsz_proof(B: Backend, out: dict) -> dict:
+    """open_shared_proof under scheme "gsz": the product check over what is still queued, then every evaluation through czk_fr_gsz_open with bound t
+    and every commitment / opening proof as the interpolation in the exponent: the value is size_inv sum_j C_j, and for every coefficient k > t,
+    sum_j w^(-j k) C_j must be the point at infinity (one points_mul and one points_sum per group element)."""
+    S, g1 = B.sharing, B.czk.CZK_G1
+    B.gsz_check()
+    P, t = S.parties, S.degree
+    dom = B.ctx.share_domain_constants(P)
+    size_inv, w_inv = unmont(dom["size_inv"]), unmont(dom["group_gen_inv"])
+    ks = [0] + list(range(t + 1, P))
+    scal = np.array([[(size_inv * pow(w_inv, j * k, R_MOD) % R_MOD >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for k in ks for j in range(P)], dtype=np.uint64)
+
+    def points(c, label):
+        aff, inf = np.asarray(c[0], dtype=np.uint64), np.asarray(c[1], dtype=np.uint8)
+        if aff.shape[0] != P:
+            return c
+        terms = B.ctx.points_mul(g1, np.tile(aff, (len(ks), 1)), scal, inf=np.tile(inf, len(ks)))
+        coef = B.ctx.points_sum(g1, terms[0], [P * i for i in range(len(ks) + 1)], inf=terms[1])
+        if not all(coef[1][1:]):
+            raise SharingError(f"{label}: the parties' points do not lie on a polynomial of degree {t}")
+        return coef[0][:1], coef[1][:1]
+
+    def value(v, label):
+        v = np.asarray(v, dtype=np.uint64).reshape(-1, 4)
+        if v.shape[0] != P:
+            return v
+        lanes, opened = B.upload(v.reshape(P, 1, 4)), B.zeros(1, 1)
+        if B.ctx.fr_gsz_open(lanes.data_ptr(), P, 1, opened.data_ptr(), degree=t):
+            raise SharingError(f"{label}: the parties' values do not lie on a polynomial of degree {t}")
+        return B.download(opened).reshape(1, 4)
+
+    def walk(x, label):
+        if isinstance(x, dict):
+            return {k: (value(v, label + "." + k) if k == "value" and not isinstance(v, dict) else walk(v, label + "." + k)) for k, v in x.items()}
+        if isinstance(x, tuple) and len(x) == 2 and all(isinstance(a, np.ndarray) for a in x) and x[0].ndim == 2 and x[0].shape[1] == 12:
+            return points(x, label)
+        if isinstance(x, (list, tuple)):
+            return type(x)(walk(v, label) for v in x)
+        if isinstance(x, np.ndarray) and x.shape == (P, 4):
             return value(x, label)
         return x
     return walk(out, "proof")
@@ -1117,6 +1256,8 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
         def val(pend):
             v = resolved(pend)
             if sharing is not None and v.shape[0] == sharing.lanes:
+                if sharing.scheme == "gsz":                      # p(0) of the interpolating polynomial: the mean of the lanes (open_shared_proof checks the degree)
+                    return sum(unmont(v[ln]) for ln in range(sharing.lanes)) * pow(sharing.parties, -1, R_MOD) % R_MOD
                 return sum(unmont(v[ln]) for ln in range(0, sharing.lanes, sharing.lpp)) % R_MOD
             return unmont(v[0])
         inv = lambda v: pow(v % R_MOD, -1, R_MOD)                # noqa: E731

@@ -374,7 +374,7 @@ int czk_gsz_batch_open(czk_net* net, const uint64_t* val, size_t n, const uint32
 /* ---- products, inverses and running products of SHARED vectors (mpc-algebra/src/share/field.rs) ------------------------------------ */
 /* FieldShare::batch_mul (:97-127), batch_inv (:135-148) and partial_products (:163-182) as one call each on device lanes, for additive shares
  * (lpp = 1 lane per party) and SPDZ shares (lpp = 2: lane lpp p = party p's sh, lane lpp p + 1 = its mac -- czk_spdz_open_combine's order).
- * batch_div is czk_share_batch_mul after czk_share_batch_inv.  GSZ shares are not covered.
+ * batch_div is czk_share_batch_mul after czk_share_batch_inv.  GSZ shares have calls of their own: czk_gsz_share_* below.
  *   lanes form (czk_share_*)     all `parties` (1..32) parties' lanes on this GPU: every vector is L = lpp parties lanes.  Nothing leaves the device
  *                                but the two counts.  mac_shares: parties x 4 limbs, one Montgomery Fr per party, HOST (NULL allowed for lpp = 1).
  *   net form (czk_net_share_*)   one party per communicator: every vector is this party's lpp lanes; the opens go through czk_add_batch_open
@@ -419,6 +419,49 @@ int czk_net_share_batch_inv(czk_net* net, size_t lpp, const uint64_t* mac_share,
 int czk_net_share_partial_products(czk_net* net, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
                                    const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t n, int flags, uint64_t* out_bad,
                                    uint64_t* out_zero);
+
+/* ---- products, inverses, running products and the product check of GSZ (Shamir) SHARED vectors (mpc-algebra/src/share/gsz20/mod.rs) ---- */
+/* gsz20's batch_mult (:559-594), batch_inv (:325-342), partial_products (:343-366) and the malicious-security product check hadamard_check ->
+ * ip_check -> ip_compress / ip_compute (:596-808) as one call each, in the lanes form: all `parties` (1..96, a size czk_share_domain_constants
+ * accepts) parties' lanes on this GPU.  A GSZ vector is `parties` lanes of n Fr, party-major, lanes n elements apart; party j's lane holds p(w^j),
+ * w = czk_share_domain_constants' group_gen.  Nothing leaves the device but the counts and the verdict.  The product check between processes and
+ * one-party-per-communicator forms of these calls are not built: a czk_net party composes czk_gsz_batch_king_compute and czk_gsz_batch_open.
+ * `degree`: the operands' degree d (normally t = (parties - 1) / 2).  The king's bound on x y + r2 is 2 d; results are shares of degree d.
+ * Material: the caller's, in the same lane order, consumed in the reference's order (czk_gsz_material_counts reports D and Rn):
+ *   doubles_r / doubles_r2   D double shares (:395-406), lanes D elements apart: the SAME random value under a polynomial of degree d and one of 2 d
+ *   rands                    Rn random shares of degree d (:383-388), lanes Rn elements apart
+ *   CZK_GSZ_OP_MUL               D = n, Rn = 0
+ *   CZK_GSZ_OP_INV               D = n, Rn = n           random share i masks element i (rs of :329); double i multiplies x_i rs_i
+ *   CZK_GSZ_OP_PARTIAL_PRODUCTS  D = 5 n + 1, Rn = 3 n + 2   rands [0, n] are m, [n + 1, 2 n + 1] batch_inv(m)'s, [2 n + 2, 3 n + 1] the inner batch_inv's;
+ *                                doubles [0, n] batch_inv(m), then n each for m x, (m x) m_inv, m_0 m_inv and the inner batch_inv (m_inv is itself a
+ *                                batch_inv here, unlike share/field.rs)
+ *   CZK_GSZ_OP_PRODUCT_CHECK     R = ceil(log2 n) (0 for n = 1): D = 2 R + 4, Rn = R + 3.  rands: the hadamard coin, one coin per round, xr, yr; doubles:
+ *                                ip_l and ip3 per round, then mult(xr, yr), mult(x, xr), mult(y, yr), mult(ip, ip_r) (:779-782)
+ * Values (every output lane equals the reference's arithmetic for that party, limb for limb; tests/gsz_mul_model.py restates it):
+ *   batch_mul          out_j = open_2d(x y + r2) - r_j: the king sends the opened value itself to every party (:478, :509)
+ *   batch_inv          out_j = rs_j / open_d(batch_mul(x, rs))
+ *   partial_products   out_i = shares of x_0 ... x_i, exactly :343-366
+ *   product_check      *out_ok = 1 when the final x y == z of :786 holds for the triples (xs_i, ys_i, zs_i), 0 when it does not (a result, not an error).
+ *                      xs, ys, zs are not modified.  n < 2^32.
+ * Degrees follow the TRUE degrees, where the reference's add / sub leave `degree` alone (rzs_sum stays "degree 0", :605-610): a sum of degree-d shares
+ * is a degree-d share, every mult of the check bounds at 2 d and every open at d.
+ * *out_bad (host): opens whose interpolating polynomial exceeded its bound (the king's, 2 d, and plain opens, d), over the whole call; the reference asserts.
+ * *out_zero (host): as for czk_share_batch_inv.  All are read back once, at the end of the call (it blocks); the check's rounds run without a host
+ * synchronisation in between.  n = 0: CZK_OK, nothing touched (*out_ok = 1).  NULL vectors with work to do: CZK_ERR_ARG; no share domain of that size
+ * (parties = 0, 5, ...), parties > 96, byte counts that overflow: CZK_ERR_SIZE.  `out` must not overlap an input.  Workspace: the staging pool. */
+#define CZK_GSZ_OP_MUL 0
+#define CZK_GSZ_OP_INV 1
+#define CZK_GSZ_OP_PARTIAL_PRODUCTS 2
+#define CZK_GSZ_OP_PRODUCT_CHECK 3
+int czk_gsz_material_counts(int op, size_t n, size_t* doubles, size_t* rands);
+int czk_gsz_share_batch_mul(czk_ctx* ctx, size_t parties, unsigned degree, const uint64_t* x, const uint64_t* y, const uint64_t* doubles_r,
+                            const uint64_t* doubles_r2, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_gsz_share_batch_inv(czk_ctx* ctx, size_t parties, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                            const uint64_t* rands, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_gsz_share_partial_products(czk_ctx* ctx, size_t parties, unsigned degree, const uint64_t* x, const uint64_t* doubles_r,
+                                   const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_gsz_product_check(czk_ctx* ctx, size_t parties, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t n,
+                          const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad);
 
 /* The king's side of king_compute (mpc-algebra/src/channel.rs:77-80; gsz20's degree reduction, share/gsz20/mod.rs:470-500): every
  * party's n Fr to the king, who receives world x n (device, party order) -- czk_net_send_to_king on Fr lanes -- and the way back. */

@@ -121,6 +121,40 @@ class Context {
         if (c.bad) throw Panic(CZK_ERR_CHECK, std::string(what) + ": assertion failed: sum.is_zero() (SPDZ MAC check, share/spdz.rs:183) on " + std::to_string(c.bad) + " values");
         if (c.zero) throw Panic(CZK_ERR_CHECK, std::string(what) + ": called `Option::unwrap()` on a `None` value (inverse of zero, share/field.rs:141) on " + std::to_string(c.zero) + " values");
     }
+    // gsz20's batch_mult / batch_inv / partial_products (share/gsz20/mod.rs:559-594, :325-366) and its product check (:596-808) with every party's
+    // lane on this GPU (czk_gsz_*, czk.h): device pointers, `parties` lanes per vector.  A degree violation panics like open_degree_vec's assert, a
+    // zero divisor like the unwrap, a failed check like the assert_eq of :786.
+    void gsz_material_counts(int op, size_t n, size_t* doubles, size_t* rands) const { check(czk_gsz_material_counts(op, n, doubles, rands)); }
+    void gsz_share_batch_mul(size_t parties, unsigned degree, const uint64_t* x, const uint64_t* y, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                             uint64_t* out, size_t n) const {
+        ShareCounts c;
+        check(czk_gsz_share_batch_mul(ctx_, parties, degree, x, y, doubles_r, doubles_r2, out, n, &c.bad, &c.zero));
+        gsz_assert(c, "gsz batch_mult");
+    }
+    void gsz_share_batch_inv(size_t parties, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands,
+                             uint64_t* out, size_t n) const {
+        ShareCounts c;
+        check(czk_gsz_share_batch_inv(ctx_, parties, degree, x, doubles_r, doubles_r2, rands, out, n, &c.bad, &c.zero));
+        gsz_assert(c, "gsz batch_inv");
+    }
+    void gsz_share_partial_products(size_t parties, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                                    const uint64_t* rands, uint64_t* out, size_t n) const {
+        ShareCounts c;
+        check(czk_gsz_share_partial_products(ctx_, parties, degree, x, doubles_r, doubles_r2, rands, out, n, &c.bad, &c.zero));
+        gsz_assert(c, "gsz partial_products");
+    }
+    void gsz_product_check(size_t parties, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t n, const uint64_t* doubles_r,
+                           const uint64_t* doubles_r2, const uint64_t* rands) const {
+        ShareCounts c;
+        uint64_t ok = 0;
+        check(czk_gsz_product_check(ctx_, parties, degree, xs, ys, zs, n, doubles_r, doubles_r2, rands, &ok, &c.bad));
+        gsz_assert(c, "gsz product check");
+        if (!ok) throw Panic(CZK_ERR_CHECK, "gsz product check: assertion failed: `(left == right)` (x * y == z, share/gsz20/mod.rs:786)");
+    }
+    static void gsz_assert(const ShareCounts& c, const char* what) {
+        if (c.bad) throw Panic(CZK_ERR_CHECK, std::string(what) + ": polynomial exceeds its degree bound (share/gsz20/mod.rs:449) on " + std::to_string(c.bad) + " opens");
+        if (c.zero) throw Panic(CZK_ERR_CHECK, std::string(what) + ": called `Option::unwrap()` on a `None` value (inverse of zero, share/gsz20/mod.rs:333) on " + std::to_string(c.zero) + " values");
+    }
 
   private:
     static const uint64_t* mac_limbs(const std::vector<Fr>& mac_shares, size_t lpp, size_t parties) {

@@ -81,6 +81,10 @@ pub const CZK_OPEN_COMMIT_TREE: c_int = 2; // #define
 pub const CZK_SHARE_OP_MUL: c_int = 0; // #define
 pub const CZK_SHARE_OP_INV: c_int = 1; // #define
 pub const CZK_SHARE_OP_PARTIAL_PRODUCTS: c_int = 2; // #define
+pub const CZK_GSZ_OP_MUL: c_int = 0; // #define
+pub const CZK_GSZ_OP_INV: c_int = 1; // #define
+pub const CZK_GSZ_OP_PARTIAL_PRODUCTS: c_int = 2; // #define
+pub const CZK_GSZ_OP_PRODUCT_CHECK: c_int = 3; // #define
 
 #[link(name = "czk_hip")]
 extern "C" {
@@ -147,6 +151,11 @@ extern "C" {
     pub fn czk_net_share_batch_mul(net: *mut czk_net, lpp: usize, mac_share: *const u64, x: *const u64, y: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, flags: c_int, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
     pub fn czk_net_share_batch_inv(net: *mut czk_net, lpp: usize, mac_share: *const u64, x: *const u64, pb: *const u64, pc: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, flags: c_int, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
     pub fn czk_net_share_partial_products(net: *mut czk_net, lpp: usize, mac_share: *const u64, x: *const u64, pb: *const u64, pc: *const u64, tx: *const u64, ty: *const u64, tz: *const u64, out: *mut u64, n: usize, flags: c_int, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_gsz_material_counts(op: c_int, n: usize, doubles: *mut usize, rands: *mut usize) -> c_int;
+    pub fn czk_gsz_share_batch_mul(ctx: *mut czk_ctx, parties: usize, degree: c_uint, x: *const u64, y: *const u64, doubles_r: *const u64, doubles_r2: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_gsz_share_batch_inv(ctx: *mut czk_ctx, parties: usize, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_gsz_share_partial_products(ctx: *mut czk_ctx, parties: usize, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_gsz_product_check(ctx: *mut czk_ctx, parties: usize, degree: c_uint, xs: *const u64, ys: *const u64, zs: *const u64, n: usize, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out_ok: *mut u64, out_bad: *mut u64) -> c_int;
     pub fn czk_fr_send_to_king(net: *mut czk_net, x: *const u64, n: usize, gathered: *mut u64) -> c_int;
     pub fn czk_fr_recv_from_king(net: *mut czk_net, parts: *const u64, n: usize, out: *mut u64) -> c_int;
     pub fn czk_gsz_batch_king_compute(net: *mut czk_net, val: *const u64, n: usize, degrees: *const u32, degree: c_uint, out: *mut u64, out_bad: *mut u64) -> c_int;
