@@ -1155,6 +1155,31 @@ class Net:
         self._ck(self._L.czk_gsz_batch_king_compute(self._h, _ptr(val_ptr), C.c_size_t(n), _ptr(degrees_ptr), C.c_uint(degree), _ptr(out_ptr), C.byref(bad)))
         return bad.value
 
+    # ---- gsz20's products and product check, this party's ONE lane (czk_net_gsz_*, czk.h): material = its lane of the lanes-form material --------
+    def _gsz_call(self, fn, degree, ptrs, n):
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._ck(fn(self._h, C.c_uint(degree), *[_ptr(p) for p in ptrs], C.c_size_t(n), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def gsz_share_batch_mul(self, degree: int, x_ptr, y_ptr, doubles_r_ptr, doubles_r2_ptr, out_ptr, n: int):
+        """czk_net_gsz_share_batch_mul -> (degree violations this rank saw, 0)"""
+        return self._gsz_call(self._L.czk_net_gsz_share_batch_mul, degree, (x_ptr, y_ptr, doubles_r_ptr, doubles_r2_ptr, out_ptr), n)
+
+    def gsz_share_batch_inv(self, degree: int, x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr, n: int):
+        """czk_net_gsz_share_batch_inv -> (degree violations this rank saw, zero divisors)"""
+        return self._gsz_call(self._L.czk_net_gsz_share_batch_inv, degree, (x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr), n)
+
+    def gsz_share_partial_products(self, degree: int, x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr, n: int):
+        """czk_net_gsz_share_partial_products -> (degree violations this rank saw, zero divisors)"""
+        return self._gsz_call(self._L.czk_net_gsz_share_partial_products, degree, (x_ptr, doubles_r_ptr, doubles_r2_ptr, rands_ptr, out_ptr), n)
+
+    def gsz_product_check(self, degree: int, xs_ptr, ys_ptr, zs_ptr, n: int, doubles_r_ptr, doubles_r2_ptr, rands_ptr):
+        """czk_net_gsz_product_check over n triples -> (ok, degree violations this rank saw); ok is the same on every rank"""
+        ok, bad = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.czk_net_gsz_product_check(self._h, C.c_uint(degree), _ptr(xs_ptr), _ptr(ys_ptr), _ptr(zs_ptr), C.c_size_t(n), _ptr(doubles_r_ptr),
+                                                   _ptr(doubles_r2_ptr), _ptr(rands_ptr), C.byref(ok), C.byref(bad)))
+        return bool(ok.value), bad.value
+
     def fr_send_to_king(self, x_ptr, n: int, gathered_ptr):
         self._ck(self._L.czk_fr_send_to_king(self._h, _ptr(x_ptr), C.c_size_t(n), _ptr(gathered_ptr)))
 

@@ -369,6 +369,26 @@ int share_combine_launch(czk_ctx* ctx, unsigned lpp, bool king, const Fr& mac_sh
 int share_scale_launch(czk_ctx* ctx, unsigned lanes, ShareVec c, const u64* k, const u64* prefix, u64* out, size_t out_stride, size_t n);
 // implemented in share.hip: builds and uploads ctx->share_tab for `parties` (stream order); CZK_ERR_SIZE when the share domain does not exist
 int gsz_open_table(czk_ctx* ctx, size_t parties);
+// czk_fr_gsz_open's launch without its read-back: violations add to the device counter `bad` (ctx->share_cnt for the protocols that read back once)
+int gsz_open_enqueue(czk_ctx* ctx, const u64* shares, size_t parties, size_t n, const uint32_t* degrees, unsigned degree, u64* out_value, unsigned long long* bad);
+// implemented in gsz_mul.hip: the party side of the one-party-per-communicator GSZ calls (net.hip), one lane, everything enqueued on ctx->stream.
+int gsz_net_mask_launch(czk_ctx* ctx, ShareVec x, ShareVec y, const u64* r2, u64* d, size_t n);   // d = x y + r2: what goes to the king
+int gsz_net_unmask_launch(czk_ctx* ctx, const u64* v, const u64* r, u64* out, size_t n);          // out = v - r: the king's answer made a share
+// One party's product check between its exchanges.  net.hip moves c.wire to the king, his answer to c.king, opened values to c.opened and broadcasts c.blind.
+struct GszNetCheck {
+    static constexpr size_t SLOT = 4;   // elements per wire buffer (at most 3 travel at once)
+    const u64 *dr, *dr2, *rands;
+    u64 *xw, *yw, *pow, *part, *hpart, *ip, *coin, *wire, *king, *opened, *blind;
+    const u64* ysrc;
+    size_t n, m, d0, r0;                // m: the folded length; d0 / r0: the next double and random share
+    bool ip_summed;
+};
+size_t gsz_net_check_ws(czk_ctx* ctx, size_t n);   // workspace, in elements
+void gsz_net_check_carve(czk_ctx* ctx, GszNetCheck& c, u64* ws, size_t n, const u64* dr, const u64* dr2, const u64* rands);
+int gsz_net_check_hadamard(czk_ctx* ctx, GszNetCheck& c, const u64* xs, const u64* ys, const u64* zs);   // the hadamard coin is in c.coin
+int gsz_net_check_round_send(czk_ctx* ctx, GszNetCheck& c);   // -> c.wire[0, 2)
+int gsz_net_check_round_recv(czk_ctx* ctx, GszNetCheck& c);   // c.king[0, 2), c.opened[0] -> the fold
+int gsz_net_check_final(czk_ctx* ctx, GszNetCheck& c, int step);   // steps 0..3 of the end, see gsz_mul.hip
 // implemented in ntt.hip
 // `addend` (lanes x D canonical Fr, not the lanes being transformed) rides on the last pass's store: a coset inverse transform writes
 // (coset_ifft(data) - addend) * *scale, a forward or coset forward transform writes its output + addend (scale unused).  Same values as the pointwise kernels.

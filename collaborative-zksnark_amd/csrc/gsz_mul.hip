@@ -13,6 +13,10 @@
 //   powers of the hadamard coin: per-byte power tables as in pow_tables.h, but built by a kernel that READS the coin from device memory (the host
 //     never sees it before the final read-back).  A scan would need its own passes over n; a square-and-multiply per thread costs ~ 60 multiplies
 //     against the 2 parties multiplies of an element's real work.  The tables are 1024 elements and every r^i is at most three multiplies.
+//   one party per communicator (czk_net_gsz_*, host code in net.hip): the same protocols on ONE lane, the kernels cut where values cross the wire:
+//     k_gsz_net_mask (d = x y + r2, to the king) and k_gsz_net_unmask (out = v - r, from his answer) for the products; for the check the one-lane
+//     instantiations of k_gsz_hadamard / k_gsz_ip / k_gsz_fold and the single-block k_gsz_net_round_send / _round_recv / _final_send / _final_mid /
+//     _verdict in place of k_gsz_round / k_gsz_final.  The king's side is k_gsz_open (share.hip) on the gathered elements.
 // No scratch; LDS only for the block reductions and the single-block round kernels.  Counts go by vector atomics to ctx->share_cnt.
 #include "czk_internal.h"
 #include "pow_tables.h"
@@ -324,6 +328,85 @@ __global__ __launch_bounds__(256) void k_gsz_final(GszRoundArgs a, unsigned long
     }
 }
 
+// ---- one party per communicator (czk_net_gsz_*, host code in net.hip): this party's ONE lane, the kernels split at the wire ---------------------
+// what a party sends to the king in a batch_mult: d = x y + r2 (:570-577)
+__global__ __launch_bounds__(256) void k_gsz_net_mask(ShareVec x, ShareVec y, const u64* r2, u64* d, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        g_store(d, i, fp_add(fp_mul(gv_load(x, 0, i), gv_load(y, 0, i)), g_load(r2, i)));
+}
+// ... and what it makes of the king's answer: out = v - r (:580-592)
+__global__ __launch_bounds__(256) void k_gsz_net_unmask(const u64* v, const u64* r, u64* out, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        g_store(out, i, fp_sub(g_load(v, i), g_load(r, i)));
+}
+
+// k_gsz_round / k_gsz_final for one lane, cut where the values cross the wire.  `wire` leaves for the king, `king` is his answer, `opened` what a
+// broadcast opened, `blind` the three blinded shares of the last open.
+struct GszNetArgs {
+    const u64 *dr, *dr2, *rands;   // this party's lanes of the material
+    size_t d0, r0;                 // the first double and random share the step consumes
+    const u64* part;               // k_gsz_ip<1>'s partials
+    unsigned nblocks;
+    const u64* ip_part;            // non-null: the running inner product is still k_gsz_hadamard<1>'s partials
+    unsigned ip_blocks;
+    u64 *ip, *coin;                // device state: this lane's running inner product and the latest coin
+    u64* wire;
+    const u64 *king, *opened;
+    u64* blind;
+    const u64 *x, *y;              // the one element left of each folded vector
+    Fr inv2;
+};
+// before the king: ip_l + r2 and ip3 + r2 of the round (ip_compute, :802-804) from the block partials; the first round also settles the running inner product
+__global__ __launch_bounds__(256) void k_gsz_net_round_send(GszNetArgs a) {
+    __shared__ Fr sm[4];
+    if (a.ip_part) {
+        const Fr s = gsz_sum_partials(a.ip_part, a.ip_blocks, 1, 0, sm);
+        if (threadIdx.x == 0) g_store(a.ip, 0, s);
+    }
+    const Fr sl = gsz_sum_partials(a.part, a.nblocks, 2, 0, sm), s3 = gsz_sum_partials(a.part, a.nblocks, 2, 1, sm);
+    if (threadIdx.x == 0) {
+        g_store(a.wire, 0, fp_add(sl, g_load(a.dr2, a.d0)));
+        g_store(a.wire, 1, fp_add(s3, g_load(a.dr2, a.d0 + 1)));
+    }
+}
+// after the king and the coin's open: ip_r = ip - ip_l (:758-762), the parabola through (1, ip_l), (2, ip_r), (3, ip3) at the coin (:717-731)
+__global__ __launch_bounds__(64) void k_gsz_net_round_recv(GszNetArgs a) {
+    if (threadIdx.x) return;
+    const Fr c = g_load(a.opened, 0);
+    const Fr one = Fr::one(), two = fp_dbl(one), three = fp_add(two, one);
+    const Fr c1 = fp_sub(c, one), c2 = fp_sub(c, two), c3 = fp_sub(c, three);
+    const Fr f1 = fp_mul(fp_mul(c2, c3), a.inv2), f2 = fp_neg(fp_mul(c1, c3)), f3 = fp_mul(fp_mul(c1, c2), a.inv2);
+    const Fr ipl = fp_sub(g_load(a.king, 0), g_load(a.dr, a.d0)), ip3 = fp_sub(g_load(a.king, 1), g_load(a.dr, a.d0 + 1)), ipr = fp_sub(g_load(a.ip, 0), ipl);
+    g_store(a.ip, 0, fp_add(fp_add(fp_mul(f1, ipl), fp_mul(f2, ipr)), fp_mul(f3, ip3)));
+    g_store(a.coin, 0, c);
+}
+// the end (:775-786), first trip: mult(xr, yr), mult(x, xr), mult(y, yr) masked; n = 1 comes here with the hadamard partials still unsummed
+__global__ __launch_bounds__(256) void k_gsz_net_final_send(GszNetArgs a) {
+    __shared__ Fr sm[4];
+    if (a.ip_part) {
+        const Fr s = gsz_sum_partials(a.ip_part, a.ip_blocks, 1, 0, sm);
+        if (threadIdx.x == 0) g_store(a.ip, 0, s);
+    }
+    if (threadIdx.x) return;
+    const Fr x = g_load(a.x, 0), y = g_load(a.y, 0), xr = g_load(a.rands, a.r0), yr = g_load(a.rands, a.r0 + 1);
+    g_store(a.wire, 0, fp_add(fp_mul(xr, yr), g_load(a.dr2, a.d0)));
+    g_store(a.wire, 1, fp_add(fp_mul(x, xr), g_load(a.dr2, a.d0 + 1)));
+    g_store(a.wire, 2, fp_add(fp_mul(y, yr), g_load(a.dr2, a.d0 + 2)));
+}
+// second trip: mult(ip, ip_r) masked, ip_r = the first trip's mult(xr, yr); the other two answers are the blinded x and y
+__global__ __launch_bounds__(64) void k_gsz_net_final_mid(GszNetArgs a) {
+    if (threadIdx.x) return;
+    const Fr ipr = fp_sub(g_load(a.king, 0), g_load(a.dr, a.d0));
+    g_store(a.wire, 0, fp_add(fp_mul(g_load(a.ip, 0), ipr), g_load(a.dr2, a.d0 + 3)));
+    g_store(a.blind, 0, fp_sub(g_load(a.king, 1), g_load(a.dr, a.d0 + 1)));
+    g_store(a.blind, 1, fp_sub(g_load(a.king, 2), g_load(a.dr, a.d0 + 2)));
+}
+// x y == z on the three opened values (:786): cnt[1] = 1 when it fails
+__global__ __launch_bounds__(64) void k_gsz_net_verdict(const u64* opened, unsigned long long* cnt) {
+    if (threadIdx.x) return;
+    if (!fp_sub(fp_mul(g_load(opened, 0), g_load(opened, 1)), g_load(opened, 2)).is_zero()) atomicExch(cnt + 1, 1ull);
+}
+
 static unsigned gsz_mul_grid(czk_ctx* ctx, size_t n) {
     size_t blocks = (n + 255) / 256;
     const size_t cap = GSZ_MUL_BLOCKS_PER_CU * (size_t)ctx->num_cu;
@@ -389,6 +472,98 @@ static unsigned ceil_log2(size_t n) {
         else if ((P) <= 6) hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__);             \
         else hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__);                           \
     } while (0)
+
+// ---- the party side of czk_net_gsz_* (declared in czk_internal.h; every function enqueues on ctx->stream and returns) ------------------------------
+// a party sweeps ONE lane: instantiations of their own (the lanes form never takes fewer than 3 lanes per sweep, and its kernels stay as they are)
+constexpr auto k_gsz_hadamard_lane = k_gsz_hadamard<1>;
+constexpr auto k_gsz_ip_lane = k_gsz_ip<1>;
+int gsz_net_mask_launch(czk_ctx* ctx, ShareVec x, ShareVec y, const u64* r2, u64* d, size_t n) {
+    ProfScope ps(ctx, "gsz_net_mask");
+    hipLaunchKernelGGL(k_gsz_net_mask, dim3(gsz_mul_grid(ctx, n)), dim3(256), 0, ctx->stream, x, y, r2, d, n);
+    CZK_HIP(ctx, hipGetLastError());
+    return CZK_OK;
+}
+int gsz_net_unmask_launch(czk_ctx* ctx, const u64* v, const u64* r, u64* out, size_t n) {
+    ProfScope ps(ctx, "gsz_net_unmask");
+    hipLaunchKernelGGL(k_gsz_net_unmask, dim3(gsz_mul_grid(ctx, n)), dim3(256), 0, ctx->stream, v, r, out, n);
+    CZK_HIP(ctx, hipGetLastError());
+    return CZK_OK;
+}
+
+size_t gsz_net_check_ws(czk_ctx* ctx, size_t n) { return 2 * n + 1024 + (size_t)3 * gsz_mul_grid(ctx, n) + 2 + 4 * GszNetCheck::SLOT; }
+
+void gsz_net_check_carve(czk_ctx* ctx, GszNetCheck& c, u64* ws, size_t n, const u64* dr, const u64* dr2, const u64* rands) {
+    const size_t g0 = gsz_mul_grid(ctx, n);
+    c.n = n, c.dr = dr, c.dr2 = dr2, c.rands = rands;
+    c.xw = ws, c.yw = c.xw + 4 * n, c.pow = c.yw + 4 * n, c.part = c.pow + 4 * 1024, c.hpart = c.part + 4 * 2 * g0, c.ip = c.hpart + 4 * g0, c.coin = c.ip + 4;
+    c.wire = c.coin + 4, c.king = c.wire + 4 * GszNetCheck::SLOT, c.opened = c.king + 4 * GszNetCheck::SLOT, c.blind = c.opened + 4 * GszNetCheck::SLOT;
+    c.ysrc = nullptr, c.m = n, c.d0 = 0, c.r0 = 1, c.ip_summed = false;
+}
+
+static GszNetArgs gsz_net_args(const GszNetCheck& c, unsigned ip_blocks) {
+    GszNetArgs a;
+    a.dr = c.dr, a.dr2 = c.dr2, a.rands = c.rands, a.d0 = c.d0, a.r0 = c.r0;
+    a.part = c.part, a.nblocks = 0;
+    a.ip_part = c.ip_summed ? nullptr : c.hpart, a.ip_blocks = ip_blocks;
+    a.ip = c.ip, a.coin = c.coin, a.wire = c.wire, a.king = c.king, a.opened = c.opened, a.blind = c.blind;
+    a.x = c.xw, a.y = c.ysrc;
+    a.inv2 = fp_inv(fp_dbl(Fr::one()));
+    return a;
+}
+
+// the hadamard coin is in c.coin: its power tables, then xw = r^i x_i and the partial sums of r^i z_i
+int gsz_net_check_hadamard(czk_ctx* ctx, GszNetCheck& c, const u64* xs, const u64* ys, const u64* zs) {
+    unsigned nb = 1;
+    while (nb < 4 && ((c.n - 1) >> (8 * nb))) nb++;
+    ProfScope ps(ctx, "gsz_net_check");
+    hipLaunchKernelGGL(k_gsz_pow_tables, dim3(4), dim3(256), 0, ctx->stream, c.pow, (const u64*)c.coin);
+    hipLaunchKernelGGL(k_gsz_hadamard_lane, dim3(gsz_mul_grid(ctx, c.n)), dim3(256), 0, ctx->stream, xs, zs, c.xw, (const u64*)c.pow, nb, c.n, 1u, c.hpart);
+    CZK_HIP(ctx, hipGetLastError());
+    c.ysrc = ys;   // the first round reads y where the caller left it
+    return CZK_OK;
+}
+// a round's local pass: both inner products of this lane, c.wire[0, 2) = ip_l + r2, ip3 + r2
+int gsz_net_check_round_send(czk_ctx* ctx, GszNetCheck& c) {
+    const size_t h = (c.m + 1) / 2;
+    const unsigned g = gsz_mul_grid(ctx, h);
+    GszNetArgs a = gsz_net_args(c, gsz_mul_grid(ctx, c.n));
+    a.nblocks = g;
+    ProfScope ps(ctx, "gsz_net_check");
+    hipLaunchKernelGGL(k_gsz_ip_lane, dim3(g), dim3(256), 0, ctx->stream, (const u64*)c.xw, c.ysrc, c.n, c.m, h, 1u, c.part);
+    hipLaunchKernelGGL(k_gsz_net_round_send, dim3(1), dim3(256), 0, ctx->stream, a);
+    CZK_HIP(ctx, hipGetLastError());
+    c.ip_summed = true;
+    return CZK_OK;
+}
+// c.king[0, 2) and c.opened[0] (the round's coin) have arrived: the new running inner product, the fold; on to the next round's material
+int gsz_net_check_round_recv(czk_ctx* ctx, GszNetCheck& c) {
+    const size_t h = (c.m + 1) / 2;
+    const GszNetArgs a = gsz_net_args(c, 0);
+    ProfScope ps(ctx, "gsz_net_check");
+    hipLaunchKernelGGL(k_gsz_net_round_recv, dim3(1), dim3(64), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_gsz_fold, dim3(gsz_mul_grid(ctx, h)), dim3(256), 0, ctx->stream, (const u64*)c.xw, c.xw, c.ysrc, c.yw, c.n, c.m, h, 1u, (const u64*)c.coin);
+    CZK_HIP(ctx, hipGetLastError());
+    c.ysrc = c.yw, c.m = h, c.d0 += 2, c.r0 += 1;
+    return CZK_OK;
+}
+// the end: step 0 -> c.wire[0, 3); step 1 (c.king[0, 3) arrived) -> c.wire[0], c.blind[0, 2); step 2 (c.king[0] arrived) -> c.blind[2];
+// step 3 (c.opened[0, 3) arrived) -> the verdict in ctx->share_cnt[1]
+int gsz_net_check_final(czk_ctx* ctx, GszNetCheck& c, int step) {
+    const GszNetArgs a = gsz_net_args(c, gsz_mul_grid(ctx, c.n));
+    ProfScope ps(ctx, "gsz_net_check");
+    if (step == 0) {
+        hipLaunchKernelGGL(k_gsz_net_final_send, dim3(1), dim3(256), 0, ctx->stream, a);
+        c.ip_summed = true;
+    } else if (step == 1) {
+        hipLaunchKernelGGL(k_gsz_net_final_mid, dim3(1), dim3(64), 0, ctx->stream, a);
+    } else if (step == 2) {
+        hipLaunchKernelGGL(k_gsz_net_unmask, dim3(1), dim3(256), 0, ctx->stream, (const u64*)c.king, c.dr + 4 * (c.d0 + 3), c.blind + 4 * 2, (size_t)1);
+    } else {
+        hipLaunchKernelGGL(k_gsz_net_verdict, dim3(1), dim3(64), 0, ctx->stream, (const u64*)c.opened, ctx->share_cnt);
+    }
+    CZK_HIP(ctx, hipGetLastError());
+    return CZK_OK;
+}
 
 }  // namespace czk
 

@@ -11,6 +11,7 @@
 //   GszFieldShare::batch_open       share/gsz20/mod.rs:286-300, 440-466   czk_gsz_batch_open
 //   gsz20::batch_king_compute       share/gsz20/mod.rs:494-527            czk_gsz_batch_king_compute
 //   FieldShare::batch_mul / batch_inv / partial_products  share/field.rs:97-182   czk_net_share_batch_mul / _batch_inv / _partial_products
+//   gsz20 batch_mult / batch_inv / partial_products / hadamard_check  share/gsz20/mod.rs:325-366, :559-808   czk_net_gsz_share_* / czk_net_gsz_product_check
 //   Vec<Fr> wire format             algebra/serialize/src/lib.rs:220-229  czk_fr_vec_serialize / _deserialize
 //
 // Two transports (include/czk.h): RCCL for one party per GPU -- every exchange is enqueued on the context's stream, so the kernels that
@@ -833,17 +834,44 @@ extern "C" int czk_add_batch_open(czk_net* n, const uint64_t* val, size_t cnt, u
     return CZK_OK;
 }
 
+namespace {
+// GszFieldShare::batch_open's exchange and launch, enqueued: `bad` non-null adds the violations to that device counter (no read-back); null makes the
+// blocking czk_fr_gsz_open count into *out_bad
+int gsz_open_trip(czk_net* n, const uint64_t* val, size_t cnt, const uint32_t* degrees, unsigned degree, uint64_t* out_value, unsigned long long* bad, uint64_t* out_bad) {
+    const size_t W = (size_t)n->world;
+    CZK_TRY(net_buf(n, n->gather, W * cnt * 32));
+    CZK_TRY(czk_net_broadcast(n, val, cnt * 32, n->gather.p, CZK_MEM_DEVICE));
+    if (bad) NET_CTX(n, gsz_open_enqueue(n->ctx, (const u64*)n->gather.p, W, cnt, degrees, degree, (u64*)out_value, bad));
+    else NET_CTX(n, czk_fr_gsz_open(n->ctx, (const uint64_t*)n->gather.p, W, cnt, degrees, degree, out_value, out_bad));
+    return CZK_OK;
+}
+// gsz20::batch_king_compute's two exchanges around the king's open, the same way
+int gsz_king_trip(czk_net* n, const uint64_t* val, size_t cnt, const uint32_t* degrees, unsigned degree, uint64_t* out, unsigned long long* bad, uint64_t* out_bad) {
+    const size_t W = (size_t)n->world;
+    const bool king = n->rank == 0;
+    // the king's scratch: world gathered lanes, then world identical answers (`vec![output; n]`, gsz20/mod.rs:508-512)
+    if (king) CZK_TRY(net_buf(n, n->gather, 2 * W * cnt * 32));
+    uint64_t* g = (uint64_t*)n->gather.p;
+    CZK_TRY(czk_net_send_to_king(n, val, cnt * 32, king ? g : nullptr, CZK_MEM_DEVICE));
+    uint64_t* ans = king ? g + 4 * W * cnt : nullptr;
+    if (king) {
+        // open_degree_vec per element, f = identity
+        if (bad) NET_CTX(n, gsz_open_enqueue(n->ctx, (const u64*)g, W, cnt, degrees, degree, (u64*)ans, bad));
+        else NET_CTX(n, czk_fr_gsz_open(n->ctx, g, W, cnt, degrees, degree, ans, out_bad));
+        for (size_t p = 1; p < W; p++)
+            NET_HIP(n, hipMemcpyAsync(ans + 4 * cnt * p, ans, cnt * 32, hipMemcpyDeviceToDevice, n->ctx->stream));
+    }
+    return czk_net_recv_from_king(n, ans, cnt * 32, out, CZK_MEM_DEVICE);
+}
+}  // namespace
+
 extern "C" int czk_gsz_batch_open(czk_net* n, const uint64_t* val, size_t cnt, const uint32_t* degrees, unsigned degree, uint64_t* out_value,
                                   uint64_t* out_bad) {
     CZK_TRY(open_args(n, val, out_value, cnt));
     if (!out_bad) return net_err(n, CZK_ERR_ARG, "czk_gsz_batch_open: null out_bad");
     *out_bad = 0;
     if (!cnt) return CZK_OK;
-    const size_t W = (size_t)n->world;
-    CZK_TRY(net_buf(n, n->gather, W * cnt * 32));
-    CZK_TRY(czk_net_broadcast(n, val, cnt * 32, n->gather.p, CZK_MEM_DEVICE));
-    NET_CTX(n, czk_fr_gsz_open(n->ctx, (const uint64_t*)n->gather.p, W, cnt, degrees, degree, out_value, out_bad));
-    return CZK_OK;
+    return gsz_open_trip(n, val, cnt, degrees, degree, out_value, nullptr, out_bad);
 }
 
 extern "C" int czk_fr_send_to_king(czk_net* n, const uint64_t* x, size_t cnt, uint64_t* gathered) {
@@ -861,19 +889,7 @@ extern "C" int czk_gsz_batch_king_compute(czk_net* n, const uint64_t* val, size_
     if (!out_bad) return net_err(n, CZK_ERR_ARG, "czk_gsz_batch_king_compute: null out_bad");
     *out_bad = 0;
     if (!cnt) return CZK_OK;
-    const size_t W = (size_t)n->world;
-    const bool king = n->rank == 0;
-    // the king's scratch: world gathered lanes, then world identical answers (`vec![output; n]`, gsz20/mod.rs:508-512)
-    if (king) CZK_TRY(net_buf(n, n->gather, 2 * W * cnt * 32));
-    uint64_t* g = (uint64_t*)n->gather.p;
-    CZK_TRY(czk_net_send_to_king(n, val, cnt * 32, king ? g : nullptr, CZK_MEM_DEVICE));
-    uint64_t* ans = king ? g + 4 * W * cnt : nullptr;
-    if (king) {
-        NET_CTX(n, czk_fr_gsz_open(n->ctx, g, W, cnt, degrees, degree, ans, out_bad));   // open_degree_vec per element, f = identity
-        for (size_t p = 1; p < W; p++)
-            NET_HIP(n, hipMemcpyAsync(ans + 4 * cnt * p, ans, cnt * 32, hipMemcpyDeviceToDevice, n->ctx->stream));
-    }
-    return czk_net_recv_from_king(n, ans, cnt * 32, out, CZK_MEM_DEVICE);
+    return gsz_king_trip(n, val, cnt, degrees, degree, out, nullptr, out_bad);
 }
 
 // ---- FieldShare::batch_mul / batch_inv / partial_products for one party per communicator (share/field.rs:97-182; kernels in share_mul.hip) -----------------
@@ -985,5 +1001,147 @@ extern "C" int czk_net_share_partial_products(czk_net* n, size_t lpp, const uint
     NET_CTX(n, share_scale_launch(n->ctx, (unsigned)lpp, ShareVec{pc + 4 * (cnt + 1), P, 1}, inv, run, out, cnt, cnt));
     NET_CTX(n, share_counters_read(n->ctx, nullptr, out_zero));
     *out_bad = s.bad;
+    return CZK_OK;
+}
+
+// ---- gsz20's batch_mult / batch_inv / partial_products and its product check for one party per communicator (share/gsz20/mod.rs:559-594, :325-366,
+// :596-808; kernels in gsz_mul.hip) ------------------------------------------------------------------------------------------------------------------------
+// The party is the communicator's rank and holds ONE lane of every vector.  Every exchange is the reference's, in its dependency order; the king's open
+// and the plain opens count their degree violations in ctx->share_cnt, read back once at the end of the call.
+namespace {
+struct NetGsz {
+    czk_net* n;
+    unsigned degree;
+    const u64 *dr, *dr2, *rands;   // this party's lanes of the material
+    unsigned long long* cnt;       // ctx->share_cnt
+};
+int net_gsz_args(czk_net* n, const char* what, unsigned degree, bool null_vec, size_t cnt, uint64_t* out_a, uint64_t* out_b, NetGsz* s, bool* work) {
+    *work = false;
+    if (!n) return CZK_ERR_ARG;
+    if (!n->ctx) return net_err(n, CZK_ERR_ARG, std::string(what) + " needs a communicator created with a context");
+    if (!out_a || !out_b) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null result output");
+    *out_a = *out_b = 0;
+    const size_t W = (size_t)n->world;
+    if (W > 96) return net_err(n, CZK_ERR_SIZE, std::string(what) + ": more than 96 parties");
+    u64 dom[12];
+    NET_CTX(n, czk_share_domain_constants(n->ctx, W, dom));   // CZK_ERR_SIZE: no share domain of that size
+    if (!cnt) return CZK_OK;
+    if (null_vec) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null argument");
+    if (cnt > ((size_t)1 << 52) / W) return net_err(n, CZK_ERR_SIZE, std::string(what) + ": the lane arrays' byte count overflows");
+    NET_HIP(n, hipSetDevice(n->ctx->device));
+    NET_CTX(n, share_counters(n->ctx));
+    s->n = n, s->degree = degree < W ? degree : (unsigned)W, s->cnt = n->ctx->share_cnt;
+    *work = true;
+    return CZK_OK;
+}
+int net_gsz_king(NetGsz& s, const u64* val, size_t cnt, u64* out) { return gsz_king_trip(s.n, val, cnt, nullptr, 2 * s.degree, out, s.cnt, nullptr); }
+int net_gsz_open(NetGsz& s, const u64* val, size_t cnt, u64* out_value) { return gsz_open_trip(s.n, val, cnt, nullptr, s.degree, out_value, s.cnt, nullptr); }
+// one batch_mult with doubles [d_first, d_first + cnt): ws = 2 cnt elements; out = this party's share of x y
+int net_gsz_mul(NetGsz& s, ShareVec x, ShareVec y, size_t d_first, u64* ws, u64* out, size_t cnt) {
+    u64 *d = ws, *v = ws + 4 * cnt;
+    NET_CTX(s.n, gsz_net_mask_launch(s.n->ctx, x, y, s.dr2 + 4 * d_first, d, cnt));
+    CZK_TRY(net_gsz_king(s, d, cnt, v));
+    NET_CTX(s.n, gsz_net_unmask_launch(s.n->ctx, v, s.dr + 4 * d_first, out, cnt));
+    return CZK_OK;
+}
+// open(batch_mult(x, y)): the product's share goes from the workspace straight to the broadcast; opened: cnt values
+int net_gsz_mul_open(NetGsz& s, ShareVec x, ShareVec y, size_t d_first, u64* ws, u64* opened, size_t cnt) {
+    CZK_TRY(net_gsz_mul(s, x, y, d_first, ws, ws, cnt));   // (v - r lands on the masked values, which the king already has)
+    return net_gsz_open(s, ws, cnt, opened);
+}
+// batch_inv (:325-342) with rs = rands [r_first, ..), doubles [d_first, ..): ws = 4 cnt elements; out = rs / open(x rs) (times prefix, when given)
+int net_gsz_inv(NetGsz& s, ShareVec x, size_t d_first, size_t r_first, u64* ws, const u64* prefix, u64* out, size_t cnt) {
+    const ShareVec rs{s.rands + 4 * r_first, 0, 1};
+    u64 *v = ws + 4 * 2 * cnt, *vinv = v + 4 * cnt;
+    CZK_TRY(net_gsz_mul_open(s, x, rs, d_first, ws, v, cnt));
+    NET_CTX(s.n, czk_fr_batch_inverse(s.n->ctx, v, cnt, nullptr, vinv, CZK_MEM_DEVICE));
+    NET_CTX(s.n, share_scale_launch(s.n->ctx, 1, rs, vinv, prefix, out, cnt, cnt));
+    return CZK_OK;
+}
+}  // namespace
+
+extern "C" int czk_net_gsz_share_batch_mul(czk_net* n, unsigned degree, const uint64_t* x, const uint64_t* y, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                                           uint64_t* out, size_t cnt, uint64_t* out_bad, uint64_t* out_zero) {
+    NetGsz s;
+    bool work;
+    CZK_TRY(net_gsz_args(n, "czk_net_gsz_share_batch_mul", degree, !x || !y || !doubles_r || !doubles_r2 || !out, cnt, out_bad, out_zero, &s, &work));
+    if (!work) return CZK_OK;
+    s.dr = doubles_r, s.dr2 = doubles_r2, s.rands = nullptr;
+    StageHold ws(n->ctx);
+    NET_CTX(n, ws.take(2 * cnt * 32));
+    CZK_TRY(net_gsz_mul(s, ShareVec{x, 0, 1}, ShareVec{y, 0, 1}, 0, (u64*)ws.b.p, out, cnt));
+    NET_CTX(n, share_counters_read(n->ctx, out_bad, out_zero));
+    return CZK_OK;
+}
+
+extern "C" int czk_net_gsz_share_batch_inv(czk_net* n, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands,
+                                           uint64_t* out, size_t cnt, uint64_t* out_bad, uint64_t* out_zero) {
+    NetGsz s;
+    bool work;
+    CZK_TRY(net_gsz_args(n, "czk_net_gsz_share_batch_inv", degree, !x || !doubles_r || !doubles_r2 || !rands || !out, cnt, out_bad, out_zero, &s, &work));
+    if (!work) return CZK_OK;
+    s.dr = doubles_r, s.dr2 = doubles_r2, s.rands = rands;
+    StageHold ws(n->ctx);
+    NET_CTX(n, ws.take(4 * cnt * 32));
+    CZK_TRY(net_gsz_inv(s, ShareVec{x, 0, 1}, 0, 0, (u64*)ws.b.p, nullptr, out, cnt));
+    NET_CTX(n, share_counters_read(n->ctx, out_bad, out_zero));
+    return CZK_OK;
+}
+
+extern "C" int czk_net_gsz_share_partial_products(czk_net* n, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                                                  const uint64_t* rands, uint64_t* out, size_t cnt, uint64_t* out_bad, uint64_t* out_zero) {
+    NetGsz s;
+    bool work;
+    CZK_TRY(net_gsz_args(n, "czk_net_gsz_share_partial_products", degree, !x || !doubles_r || !doubles_r2 || !rands || !out, cnt, out_bad, out_zero, &s, &work));
+    if (!work) return CZK_OK;
+    s.dr = doubles_r, s.dr2 = doubles_r2, s.rands = rands;
+    const size_t c1 = cnt + 1;
+    StageHold ws(n->ctx);
+    NET_CTX(n, ws.take((4 * c1 + c1 + 3 * cnt) * 32));
+    u64 *mulws = (u64*)ws.b.p, *m_inv = mulws + 4 * 4 * c1, *lane = m_inv + 4 * c1, *mxm = lane + 4 * cnt, *run = mxm + 4 * cnt;
+    const ShareVec m{rands, 0, 1}, m0{rands, 0, 0}, m_inv1{m_inv + 4, 0, 1};                                            // m = rands [0, n]; m_inv[1..]
+    CZK_TRY(net_gsz_inv(s, m, 0, cnt + 1, mulws, nullptr, m_inv, c1));                                                   // m_inv = batch_inv(m)
+    CZK_TRY(net_gsz_mul(s, m, ShareVec{x, 0, 1}, cnt + 1, mulws, lane, cnt));                                            // mx = m[..n] x
+    CZK_TRY(net_gsz_mul_open(s, ShareVec{lane, 0, 1}, m_inv1, 2 * cnt + 1, mulws, mxm, cnt));                            // open(mx m_inv[1..])
+    NET_CTX(n, czk_fr_prefix_product(n->ctx, mxm, cnt, run, CZK_MEM_DEVICE));                                            // the local loop :353-356
+    CZK_TRY(net_gsz_mul(s, m0, m_inv1, 3 * cnt + 1, mulws, lane, cnt));                                                  // mms = m_0 m_inv[1..]
+    CZK_TRY(net_gsz_inv(s, ShareVec{lane, 0, 1}, 4 * cnt + 1, 2 * cnt + 2, mulws, run, out, cnt));                       // batch_inv(mms), scaled by the running product
+    NET_CTX(n, share_counters_read(n->ctx, out_bad, out_zero));
+    return CZK_OK;
+}
+
+extern "C" int czk_net_gsz_product_check(czk_net* n, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t cnt, const uint64_t* doubles_r,
+                                         const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad) {
+    NetGsz s;
+    bool work;
+    CZK_TRY(net_gsz_args(n, "czk_net_gsz_product_check", degree, !xs || !ys || !zs || !doubles_r || !doubles_r2 || !rands, cnt, out_ok, out_bad, &s, &work));
+    *out_ok = 1;   // no triples: nothing to refute
+    if (!work) return CZK_OK;
+    if (cnt >> 32) return net_err(n, CZK_ERR_SIZE, "czk_net_gsz_product_check: more than 2^32 - 1 triples");
+    czk_ctx* ctx = n->ctx;
+    unsigned R = 0;
+    while (((size_t)1 << R) < cnt) R++;
+    StageHold ws(ctx);
+    NET_CTX(n, ws.take(gsz_net_check_ws(ctx, cnt) * 32));
+    GszNetCheck c;
+    gsz_net_check_carve(ctx, c, (u64*)ws.b.p, cnt, doubles_r, doubles_r2, rands);
+    CZK_TRY(net_gsz_open(s, rands, 1, c.coin));                       // the hadamard coin (:601): the triples were committed before the call
+    NET_CTX(n, gsz_net_check_hadamard(ctx, c, xs, ys, zs));
+    for (unsigned round = 0; round < R; round++) {
+        NET_CTX(n, gsz_net_check_round_send(ctx, c));
+        CZK_TRY(net_gsz_king(s, c.wire, 2, c.king));                  // ip_l and ip3 in ONE round trip (both ip_compute calls precede the coin, :757, :690-692)
+        CZK_TRY(net_gsz_open(s, rands + 4 * c.r0, 1, c.opened));      // only now the round's coin
+        NET_CTX(n, gsz_net_check_round_recv(ctx, c));
+    }
+    NET_CTX(n, gsz_net_check_final(ctx, c, 0));
+    CZK_TRY(net_gsz_king(s, c.wire, 3, c.king));                      // mult(xr, yr), mult(x, xr), mult(y, yr)
+    NET_CTX(n, gsz_net_check_final(ctx, c, 1));
+    CZK_TRY(net_gsz_king(s, c.wire, 1, c.king));                      // mult(ip, ip_r) needs the first trip's answer
+    NET_CTX(n, gsz_net_check_final(ctx, c, 2));
+    CZK_TRY(net_gsz_open(s, c.blind, 3, c.opened));                   // the three blinded values in one broadcast
+    NET_CTX(n, gsz_net_check_final(ctx, c, 3));
+    uint64_t failed = 0;
+    NET_CTX(n, share_counters_read(ctx, out_bad, &failed));          // the one read-back of the check
+    *out_ok = failed ? 0 : 1;
     return CZK_OK;
 }

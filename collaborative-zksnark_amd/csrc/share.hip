@@ -138,24 +138,31 @@ extern "C" int czk_fr_gsz_open(czk_ctx* ctx, const uint64_t* shares, size_t part
     CZK_TRY(czk_share_domain_constants(ctx, parties, dom));
     if (!n) return CZK_OK;
     CZK_HIP(ctx, hipSetDevice(ctx->device));
-    CZK_TRY(gsz_open_table(ctx, parties));
     if (!ctx->open_bad) CZK_HIP(ctx, hipMalloc(&ctx->open_bad, 8));
     CZK_HIP(ctx, hipMemsetAsync(ctx->open_bad, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_gsz_open, dim3(share_grid(ctx, n)), dim3(256), 0, ctx->stream, (const u64*)shares, parties, n, (const u64*)ctx->share_tab.p, degrees, degree,
-                       (u64*)out_value, ctx->open_bad);
-    CZK_HIP(ctx, hipGetLastError());
+    CZK_TRY(gsz_open_enqueue(ctx, (const u64*)shares, parties, n, degrees, degree, (u64*)out_value, ctx->open_bad));
     return count_readback(ctx, out_bad);
 }
 
+// the launch alone, for callers that keep their counts on the device (parties: a size the share domain exists for, at most 96)
+int czk::gsz_open_enqueue(czk_ctx* ctx, const u64* shares, size_t parties, size_t n, const uint32_t* degrees, unsigned degree, u64* out_value, unsigned long long* bad) {
+    CZK_TRY(gsz_open_table(ctx, parties));
+    hipLaunchKernelGGL(k_gsz_open, dim3(share_grid(ctx, n)), dim3(256), 0, ctx->stream, shares, parties, n, (const u64*)ctx->share_tab.p, degrees, degree, out_value, bad);
+    CZK_HIP(ctx, hipGetLastError());
+    return CZK_OK;
+}
+
 // ctx->share_tab = size_inv * w^(-j k) for j, k < parties, enqueued on the context's stream.  The host copy lives in the context, so it outlasts the
-// copy whatever the caller does next.
+// copy whatever the caller does next -- and says which table the device holds: `parties` fixes every entry, so a host copy of that size means the
+// same table was uploaded earlier on this stream and the call has nothing to do (a protocol of many single-element opens asks once per open).
 int czk::gsz_open_table(czk_ctx* ctx, size_t parties) {
+    if (parties && ctx->share_tab.p && ctx->share_tab_host.size() == 4 * parties * parties) return CZK_OK;
+    ctx->share_tab_host.clear();   // (stays empty when anything below fails)
     u64 dom[12];
     CZK_TRY(czk_share_domain_constants(ctx, parties, dom));
     // host arithmetic: at most 96^2 multiplies
     const Fr size_inv = host_fr(dom), winv = host_fr(dom + 8);
-    std::vector<u64>& tab = ctx->share_tab_host;
-    tab.resize(4 * parties * parties);
+    std::vector<u64> tab(4 * parties * parties);
     Fr wj = Fr::one();                                    // w^-j
     for (size_t j = 0; j < parties; j++) {
         Fr e = size_inv;                                  // size_inv * w^(-j k)
@@ -166,6 +173,10 @@ int czk::gsz_open_table(czk_ctx* ctx, size_t parties) {
         wj = fp_mul(wj, winv);
     }
     CZK_TRY(ensure_buf(ctx, ctx->share_tab, tab.size() * 8));
-    CZK_HIP(ctx, hipMemcpyAsync(ctx->share_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    ctx->share_tab_host.swap(tab);
+    if (hipMemcpyAsync(ctx->share_tab.p, ctx->share_tab_host.data(), ctx->share_tab_host.size() * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        ctx->share_tab_host.clear();
+        return set_err(ctx, CZK_ERR_HIP, "hipMemcpyAsync of the share domain's table");
+    }
     return CZK_OK;
 }

@@ -539,3 +539,53 @@ def share_batch_inv(ctx, lpp: int, mac_share, x, pb, pc, tx, ty, tz, commit: boo
 def share_partial_products(ctx, lpp: int, mac_share, x, pb, pc, tx, ty, tz, commit: bool | str = True) -> torch.Tensor:
     """this party's lanes of the running products x_0 ... x_i (share/field.rs:163-182)"""
     return _share_net_call(ctx, "share_partial_products", lpp, mac_share, (x, pb, pc, tx, ty, tz), x.shape[1], commit)
+
+
+# ---- gsz20's batch_mult / batch_inv / partial_products and the product check with one process per party (czk_net_gsz_*, include/czk.h) ---------------------
+# Every vector is this party's ONE lane, (k, 4) uint64 on the device; the material is its lane of what czk_gsz_material_counts counts.
+def _gsz_net_vecs(name: str, vecs):
+    if _NET is None:
+        raise RuntimeError(f"parallel.{name} runs over a czk_net communicator: call parallel.use_net(parallel.make_net(ctx, 'shm')) first")
+    vecs = [v.contiguous() for v in vecs]
+    if any(not v.is_cuda or v.dim() != 2 or v.shape[1] != 4 for v in vecs):
+        raise ValueError(f"parallel.{name}: every vector is this party's (k, 4) device lane")
+    return vecs
+
+
+def _gsz_net_call(ctx, name: str, degree: int, vecs, n: int):
+    vecs = _gsz_net_vecs(name, vecs)
+    out = torch.empty((n, 4), dtype=vecs[0].dtype, device=vecs[0].device)
+    for v in vecs:
+        _net_in(ctx, v)
+    bad, zero = getattr(_NET, name)(degree, *[v.data_ptr() for v in vecs], out.data_ptr(), n)
+    if bad or zero:
+        raise MpcCheckError(f"{name} of {n} shared elements: {bad} degree violation(s), {zero} zero divisor(s)")
+    return _after_consume(ctx, out)
+
+
+def gsz_share_batch_mul(ctx, degree: int, x, y, doubles_r, doubles_r2) -> torch.Tensor:
+    """this party's share of x * y (share/gsz20/mod.rs:559-594) from its shares of x, y and of n double shares"""
+    return _gsz_net_call(ctx, "gsz_share_batch_mul", degree, (x, y, doubles_r, doubles_r2), x.shape[0])
+
+
+def gsz_share_batch_inv(ctx, degree: int, x, doubles_r, doubles_r2, rands) -> torch.Tensor:
+    """this party's share of 1 / x (share/gsz20/mod.rs:325-342)"""
+    return _gsz_net_call(ctx, "gsz_share_batch_inv", degree, (x, doubles_r, doubles_r2, rands), x.shape[0])
+
+
+def gsz_share_partial_products(ctx, degree: int, x, doubles_r, doubles_r2, rands) -> torch.Tensor:
+    """this party's shares of the running products x_0 ... x_i (share/gsz20/mod.rs:343-366)"""
+    return _gsz_net_call(ctx, "gsz_share_partial_products", degree, (x, doubles_r, doubles_r2, rands), x.shape[0])
+
+
+def gsz_product_check(ctx, degree: int, xs, ys, zs, doubles_r, doubles_r2, rands) -> None:
+    """hadamard_check (share/gsz20/mod.rs:596-808) over this party's shares of the triples; raises MpcCheckError when x y == z fails or an open exceeds
+    its degree bound (the reference asserts both)"""
+    vecs = _gsz_net_vecs("gsz_product_check", (xs, ys, zs, doubles_r, doubles_r2, rands))
+    for v in vecs:
+        _net_in(ctx, v)
+    n = vecs[0].shape[0]
+    ok, bad = _NET.gsz_product_check(degree, *[v.data_ptr() for v in vecs[:3]], n, *[v.data_ptr() for v in vecs[3:]])
+    _after_consume(ctx, vecs[0])
+    if not ok or bad:
+        raise MpcCheckError(f"gsz_product_check of {n} triples: verdict {int(ok)}, {bad} degree violation(s)")

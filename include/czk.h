@@ -424,8 +424,8 @@ int czk_net_share_partial_products(czk_net* net, size_t lpp, const uint64_t* mac
 /* gsz20's batch_mult (:559-594), batch_inv (:325-342), partial_products (:343-366) and the malicious-security product check hadamard_check ->
  * ip_check -> ip_compress / ip_compute (:596-808) as one call each, in the lanes form: all `parties` (1..96, a size czk_share_domain_constants
  * accepts) parties' lanes on this GPU.  A GSZ vector is `parties` lanes of n Fr, party-major, lanes n elements apart; party j's lane holds p(w^j),
- * w = czk_share_domain_constants' group_gen.  Nothing leaves the device but the counts and the verdict.  The product check between processes and
- * one-party-per-communicator forms of these calls are not built: a czk_net party composes czk_gsz_batch_king_compute and czk_gsz_batch_open.
+ * w = czk_share_domain_constants' group_gen.  Nothing leaves the device but the counts and the verdict.  The same calls with one party per
+ * communicator, the product check between processes included, are czk_net_gsz_* below.
  * `degree`: the operands' degree d (normally t = (parties - 1) / 2).  The king's bound on x y + r2 is 2 d; results are shares of degree d.
  * Material: the caller's, in the same lane order, consumed in the reference's order (czk_gsz_material_counts reports D and Rn):
  *   doubles_r / doubles_r2   D double shares (:395-406), lanes D elements apart: the SAME random value under a polynomial of degree d and one of 2 d
@@ -462,6 +462,33 @@ int czk_gsz_share_partial_products(czk_ctx* ctx, size_t parties, unsigned degree
                                    const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
 int czk_gsz_product_check(czk_ctx* ctx, size_t parties, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t n,
                           const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad);
+/* The same four calls with one party per communicator (czk_net_gsz_*): the party is czk_net_rank(net) of czk_net_world(net) parties and every vector is
+ * its ONE lane of n Fr, CZK_MEM_DEVICE on the communicator's context.  The material is the party's own lane of the lanes-form material, counted by
+ * czk_gsz_material_counts and consumed in the same order.  Give rank j lane j of every input: its `out` is lane j of what czk_gsz_share_* writes on that
+ * material, limb for limb, and *out_ok is the lanes form's verdict on every rank.  `degree` and the degree rule are those above.
+ * Exchanges per call, as czk_net_stats counts them (a king round trip = one to_king and one from_king; R = ceil(log2 n), 0 for n = 1):
+ *   batch_mul          1 king round trip (x y + r2 at bound 2 d), no broadcast
+ *   batch_inv          1 king round trip, then 1 broadcast (open of x rs at bound d)
+ *   partial_products   5 king round trips, 3 broadcasts: the lanes form's sequence, batch_inv(m); m x; open((m x) m_inv); m_0 m_inv; batch_inv of that
+ *   product_check      R + 2 king round trips, R + 2 broadcasts: the hadamard coin (1 broadcast); per round ip_l and ip3 in ONE king round trip of two
+ *                      elements, and only then the round's coin (1 broadcast); at the end mult(xr, yr), mult(x, xr), mult(y, yr) in one king round trip,
+ *                      mult(ip, ip_r), which needs the first, in a second, and the three blinded values in one broadcast.  All n-sized passes are local;
+ *                      the wire carries 2 R + 4 elements to the king and R + 4 broadcast elements per party.  No coin travels in or before the exchange
+ *                      that carries the values it challenges.
+ * *out_bad counts what this rank can see: the king's bound (2 d) is checked on rank 0 only, as for czk_gsz_batch_king_compute; plain opens (d) are
+ * checked, and counted, on every rank.  *out_zero and *out_ok come out equal on all ranks (they follow from broadcast opens).  Counts and verdict are
+ * accumulated on the device and read back once, at the end of the call; every rank must make the same call with the same n.
+ * A communicator without a context, NULL vectors with work to do: CZK_ERR_ARG.  A world the share domain does not exist for (5, ...), more than 96
+ * parties, n >= 2^32 for the check, byte counts that overflow: CZK_ERR_SIZE.  n = 0: CZK_OK, nothing touched, *out_ok = 1.  `out` must not overlap an
+ * input; xs, ys, zs are not modified.  Workspace: the context's staging pool, and the communicator's gather scratch on the king. */
+int czk_net_gsz_share_batch_mul(czk_net* net, unsigned degree, const uint64_t* x, const uint64_t* y, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                                uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_net_gsz_share_batch_inv(czk_net* net, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                                const uint64_t* rands, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_net_gsz_share_partial_products(czk_net* net, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2,
+                                       const uint64_t* rands, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
+int czk_net_gsz_product_check(czk_net* net, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t n,
+                              const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad);
 
 /* The king's side of king_compute (mpc-algebra/src/channel.rs:77-80; gsz20's degree reduction, share/gsz20/mod.rs:470-500): every
  * party's n Fr to the king, who receives world x n (device, party order) -- czk_net_send_to_king on Fr lanes -- and the way back. */

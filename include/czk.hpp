@@ -123,7 +123,7 @@ class Context {
     }
     // gsz20's batch_mult / batch_inv / partial_products (share/gsz20/mod.rs:559-594, :325-366) and its product check (:596-808) with every party's
     // lane on this GPU (czk_gsz_*, czk.h): device pointers, `parties` lanes per vector.  A degree violation panics like open_degree_vec's assert, a
-    // zero divisor like the unwrap, a failed check like the assert_eq of :786.
+    // zero divisor like the unwrap, a failed check like the assert_eq of :786.  One party per communicator: the same names on Net.
     void gsz_material_counts(int op, size_t n, size_t* doubles, size_t* rands) const { check(czk_gsz_material_counts(op, n, doubles, rands)); }
     void gsz_share_batch_mul(size_t parties, unsigned degree, const uint64_t* x, const uint64_t* y, const uint64_t* doubles_r, const uint64_t* doubles_r2,
                              uint64_t* out, size_t n) const {
@@ -316,6 +316,34 @@ class Net {
         Context::ShareCounts c;
         check(czk_net_share_partial_products(n_, lpp, mac_share.l, x, pb, pc, tx, ty, tz, out, n, flags, &c.bad, &c.zero));
         Context::share_assert(c, "partial_products");
+    }
+    //   gsz20's batch_mult / batch_inv / partial_products and product check on this party's ONE lane (czk_net_gsz_*, czk.h): the one-party-per-communicator
+    //   form of Context::gsz_*, with its panics.  The king's degree bound panics on rank 0 only; the verdict and the zero divisors on every rank.
+    void gsz_share_batch_mul(unsigned degree, const uint64_t* x, const uint64_t* y, const uint64_t* doubles_r, const uint64_t* doubles_r2, uint64_t* out,
+                             size_t n) const {
+        Context::ShareCounts c;
+        check(czk_net_gsz_share_batch_mul(n_, degree, x, y, doubles_r, doubles_r2, out, n, &c.bad, &c.zero));
+        Context::gsz_assert(c, "gsz batch_mult");
+    }
+    void gsz_share_batch_inv(unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out,
+                             size_t n) const {
+        Context::ShareCounts c;
+        check(czk_net_gsz_share_batch_inv(n_, degree, x, doubles_r, doubles_r2, rands, out, n, &c.bad, &c.zero));
+        Context::gsz_assert(c, "gsz batch_inv");
+    }
+    void gsz_share_partial_products(unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands,
+                                    uint64_t* out, size_t n) const {
+        Context::ShareCounts c;
+        check(czk_net_gsz_share_partial_products(n_, degree, x, doubles_r, doubles_r2, rands, out, n, &c.bad, &c.zero));
+        Context::gsz_assert(c, "gsz partial_products");
+    }
+    void gsz_product_check(unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t n, const uint64_t* doubles_r,
+                           const uint64_t* doubles_r2, const uint64_t* rands) const {
+        Context::ShareCounts c;
+        uint64_t ok = 0;
+        check(czk_net_gsz_product_check(n_, degree, xs, ys, zs, n, doubles_r, doubles_r2, rands, &ok, &c.bad));
+        Context::gsz_assert(c, "gsz product check");
+        if (!ok) throw Panic(CZK_ERR_CHECK, "gsz product check: assertion failed: `(left == right)` (x * y == z, share/gsz20/mod.rs:786)");
     }
     //   GszFieldShare::batch_open (share/gsz20/mod.rs:286-300) with one degree bound for the whole vector
     void gsz_batch_open(const uint64_t* val, size_t n, unsigned degree, uint64_t* out) const {

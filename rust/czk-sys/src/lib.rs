@@ -156,6 +156,10 @@ extern "C" {
     pub fn czk_gsz_share_batch_inv(ctx: *mut czk_ctx, parties: usize, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
     pub fn czk_gsz_share_partial_products(ctx: *mut czk_ctx, parties: usize, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
     pub fn czk_gsz_product_check(ctx: *mut czk_ctx, parties: usize, degree: c_uint, xs: *const u64, ys: *const u64, zs: *const u64, n: usize, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out_ok: *mut u64, out_bad: *mut u64) -> c_int;
+    pub fn czk_net_gsz_share_batch_mul(net: *mut czk_net, degree: c_uint, x: *const u64, y: *const u64, doubles_r: *const u64, doubles_r2: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_net_gsz_share_batch_inv(net: *mut czk_net, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_net_gsz_share_partial_products(net: *mut czk_net, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
+    pub fn czk_net_gsz_product_check(net: *mut czk_net, degree: c_uint, xs: *const u64, ys: *const u64, zs: *const u64, n: usize, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out_ok: *mut u64, out_bad: *mut u64) -> c_int;
     pub fn czk_fr_send_to_king(net: *mut czk_net, x: *const u64, n: usize, gathered: *mut u64) -> c_int;
     pub fn czk_fr_recv_from_king(net: *mut czk_net, parts: *const u64, n: usize, out: *mut u64) -> c_int;
     pub fn czk_gsz_batch_king_compute(net: *mut czk_net, val: *const u64, n: usize, degrees: *const u32, degree: c_uint, out: *mut u64, out_bad: *mut u64) -> c_int;

@@ -14,9 +14,18 @@
           Reported with each: the product checks per proof, the most triples one check covered (the queue holds 3 * parties * 32 bytes of device
           memory per triple until then) and, from one more instrumented proof, the time inside the checks.
 
+  --net WORLD   instead of the above: czk_net_gsz_share_batch_mul / _batch_inv / _partial_products and czk_net_gsz_product_check with WORLD processes,
+          one party each, sharing GPU 0 over CZK_NET_IPC (device mailboxes), on n elements per party: per call the wall time on every rank between
+          two barriers (median and minimum of --reps after one warm-up; the slowest rank is the call's time), the exchanges and the bytes sent and
+          received per rank as czk_net_stats counts them.  With it, from the same run: the lanes form at WORLD parties in one process (measured
+          first, alone on the GPU), and the latency of one king round trip and of one broadcast of a single element on that transport (--lat-reps
+          of each, back to back), bare and as czk_gsz_batch_king_compute / czk_gsz_batch_open (with the open's kernel and a read-back), so that a
+          call's time can be set against its exchanges.
+
 One JSON line.
 
-    python tools/gsz_mul_bench.py [--n 786432] [--reps 5] [--log-gates 18] [--skip-plonk] [--skip-calls] [--skip-composed] [--out PATH]"""
+    python tools/gsz_mul_bench.py [--n 786432] [--reps 5] [--log-gates 18] [--skip-plonk] [--skip-calls] [--skip-composed] [--out PATH]
+    python tools/gsz_mul_bench.py --net 3 [--n 786432] [--reps 5] [--lat-reps 200] [--out PATH]"""
 import argparse
 import json
 import os
@@ -165,8 +174,131 @@ def timed(fn, reps):
     return {"ms_median": round(statistics.median(times), 3), "ms_min": round(min(times), 3)}
 
 
+NET_CALLS = ("batch_mul", "batch_inv", "partial_products", "product_check")
+
+
+def random_lanes(czk_amd, torch, ctx, parties, n, seed):
+    """-> lanes(k, roll): (parties, k, 4) device tensors of random field elements, no two of them the same memory"""
+    from czk_amd.provers import rand_fr_canonical
+    raw = torch.from_numpy(rand_fr_canonical(seed, parties * n).view(np.int64)).cuda()
+    blk = torch.empty((parties, n, 4), dtype=torch.int64, device="cuda")
+    ctx.fr_from_repr(raw.data_ptr(), out=blk.data_ptr(), n=parties * n, mem=czk_amd.CZK_MEM_DEVICE)
+    ctx.sync()
+    return lambda k, roll: torch.cat([torch.roll(blk, roll + r, 1) for r in range(-(-k // n))], dim=1)[:, :k].contiguous()
+
+
+def lanes_form(czk_amd, torch, parties, n, reps):
+    """the four lanes-form calls at `parties` parties in this process -> {call: {ms_median, ms_min}}"""
+    bd, t = czk_amd.binding, (parties - 1) // 2
+    ctx = czk_amd.Context(0)
+    lanes = random_lanes(czk_amd, torch, ctx, parties, n, 1)
+    x, y, z, out = lanes(n, 1), lanes(n, 2), lanes(n, 3), torch.empty((parties, n, 4), dtype=torch.int64, device="cuda")
+    per = {}
+    for name, op in zip(NET_CALLS, (bd.CZK_GSZ_OP_MUL, bd.CZK_GSZ_OP_INV, bd.CZK_GSZ_OP_PARTIAL_PRODUCTS, bd.CZK_GSZ_OP_PRODUCT_CHECK)):
+        nd, nr = ctx.gsz_material_counts(op, n)
+        dr, dr2, rands = lanes(nd, 4), lanes(nd, 5), lanes(max(nr, 1), 6)
+        p = [v.data_ptr() for v in (x, y, z, dr, dr2, rands, out)]
+        call = {"batch_mul": lambda: ctx.gsz_share_batch_mul(parties, t, p[0], p[1], p[3], p[4], p[6], n),
+                "batch_inv": lambda: ctx.gsz_share_batch_inv(parties, t, p[0], p[3], p[4], p[5], p[6], n),
+                "partial_products": lambda: ctx.gsz_share_partial_products(parties, t, p[0], p[3], p[4], p[5], p[6], n),
+                "product_check": lambda: ctx.gsz_product_check(parties, t, p[0], p[1], p[2], n, p[3], p[4], p[5])}[name]
+        torch.cuda.synchronize()
+        per[name] = timed(call, reps)
+        del dr, dr2, rands
+    ctx.close()
+    return per
+
+
+def net_party(rank, world, q, idb, n, reps, lat_reps):
+    """one party of --net: times the four calls on its own lane and the two single-element exchanges"""
+    os.environ["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
+    import torch
+    import czk_amd
+    bd, t = czk_amd.binding, (world - 1) // 2
+    torch.cuda.set_device(0)
+    ctx = czk_amd.Context(0)
+    slot = max(16 << 20, ((n + 1) * 32 + (1 << 20)) & ~((1 << 20) - 1))       # a whole lane per chunk step
+    net = czk_amd.Net(ctx, czk_amd.CZK_NET_IPC, rank, world, idb, options={"slot_bytes": slot, "timeout_ms": 120000})
+    lanes = random_lanes(czk_amd, torch, ctx, 1, n, 11 + rank)
+    x, y, z, out = lanes(n, 1)[0], lanes(n, 2)[0], lanes(n, 3)[0], torch.empty((n, 4), dtype=torch.int64, device="cuda")
+    per = {}
+    for name, op in zip(NET_CALLS, (bd.CZK_GSZ_OP_MUL, bd.CZK_GSZ_OP_INV, bd.CZK_GSZ_OP_PARTIAL_PRODUCTS, bd.CZK_GSZ_OP_PRODUCT_CHECK)):
+        nd, nr = ctx.gsz_material_counts(op, n)
+        dr, dr2, rands = lanes(nd, 4)[0], lanes(nd, 5)[0], lanes(max(nr, 1), 6)[0]
+        p = [v.data_ptr() for v in (x, y, z, dr, dr2, rands, out)]
+        call = {"batch_mul": lambda: net.gsz_share_batch_mul(t, p[0], p[1], p[3], p[4], p[6], n),
+                "batch_inv": lambda: net.gsz_share_batch_inv(t, p[0], p[3], p[4], p[5], p[6], n),
+                "partial_products": lambda: net.gsz_share_partial_products(t, p[0], p[3], p[4], p[5], p[6], n),
+                "product_check": lambda: net.gsz_product_check(t, p[0], p[1], p[2], n, p[3], p[4], p[5])}[name]
+        times = []
+        for rep in range(reps + 1):
+            torch.cuda.synchronize()
+            net.barrier()
+            net.stats_reset()
+            t0 = time.perf_counter()
+            call()
+            net.barrier()                                                      # the call is over when every party has its answer
+            if rep:
+                times.append((time.perf_counter() - t0) * 1e3)
+        per[name] = dict(net.stats(), ms_median=round(statistics.median(times), 3), ms_min=round(min(times), 3))
+        del dr, dr2, rands
+    one, king = out[:1], torch.empty((2 * world, 4), dtype=torch.int64, device="cuda")
+    lat = {}
+    for name, step in (("king_round_trip", lambda: (net.fr_send_to_king(one.data_ptr(), 1, king.data_ptr()), net.fr_recv_from_king(king.data_ptr(), 1, one.data_ptr()))),
+                       ("broadcast", lambda: net.broadcast(one.data_ptr(), 32, king.data_ptr(), mem=czk_amd.CZK_MEM_DEVICE)),
+                       # the same two with the open's kernel and a read-back of its count: the blocking calls a party had to compose before
+                       ("king_compute", lambda: net.gsz_batch_king_compute(one.data_ptr(), 1, one.data_ptr(), degree=2 * t)),
+                       ("batch_open", lambda: net.gsz_batch_open(one.data_ptr(), 1, king.data_ptr(), degree=t))):
+        step()
+        ctx.sync()
+        net.barrier()
+        t0 = time.perf_counter()
+        for _ in range(lat_reps):
+            step()
+        ctx.sync()
+        lat[name + "_us"] = round((time.perf_counter() - t0) * 1e6 / lat_reps, 2)
+    net.barrier()
+    net.close()
+    ctx.close()
+    q.put((rank, per, lat))
+
+
+def net_mode(a):
+    import multiprocessing as mp
+    import torch
+    import czk_amd
+    res = {"n": a.n, "world": a.net, "transport": "ipc", "device": torch.cuda.get_device_name(0)}
+    res["lanes_form"] = lanes_form(czk_amd, torch, a.net, a.n, a.reps)
+    torch.cuda.empty_cache()
+    c = mp.get_context("spawn")
+    q = c.Queue()
+    idb = czk_amd.Net.unique_id(czk_amd.CZK_NET_IPC)
+    procs = [c.Process(target=net_party, args=(r, a.net, q, idb, a.n, a.reps, a.lat_reps)) for r in range(a.net)]
+    for p in procs:
+        p.start()
+    got = []
+    while len(got) < a.net:
+        try:
+            got.append(q.get(timeout=1.0))
+        except Exception:
+            if any(p.exitcode not in (None, 0) for p in procs):
+                for p in procs:
+                    if p.is_alive():
+                        p.kill()
+                raise SystemExit("a party died: " + str([p.exitcode for p in procs]))
+    for p in procs:
+        p.join()
+    got.sort()
+    res["net"] = {name: {"ms_median": max(per[name]["ms_median"] for _, per, _ in got), "ms_min": max(per[name]["ms_min"] for _, per, _ in got),
+                         "ranks": [per[name] for _, per, _ in got]} for name in NET_CALLS}
+    res["latency"] = {k: [lat[k] for _, _, lat in got] for k in got[0][2]}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--net", type=int, default=0, metavar="WORLD")
+    ap.add_argument("--lat-reps", type=int, default=200)
     ap.add_argument("--n", type=int, default=3 << 18)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log-gates", type=int, default=18)
@@ -175,6 +307,14 @@ def main():
     ap.add_argument("--skip-composed", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.net:
+        line = json.dumps(net_mode(a))
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     import torch
     import czk_amd
     from czk_amd import polyvm
