@@ -46,6 +46,7 @@ def _share_material_counts(L, op: int, n: int):
 
 
 CZK_GSZ_OP_MUL, CZK_GSZ_OP_INV, CZK_GSZ_OP_PARTIAL_PRODUCTS, CZK_GSZ_OP_PRODUCT_CHECK = 0, 1, 2, 3   # czk_gsz_material_counts
+CZK_GSZ_DN_DOUBLES, CZK_GSZ_DN_RANDS = 0, 1   # czk_gsz_dn_*: the same value under degree d and 2 d / degree d only
 
 
 def open_commit_flags(commit) -> int:
@@ -128,6 +129,22 @@ def header_symbols() -> list[str]:
 def exported_symbols() -> list[str]:
     l = lib()
     return [s for s in header_symbols() if hasattr(l, s)]
+
+
+def _key_bytes(b, length: int):
+    """exactly `length` bytes as a ctypes array (keys and nonces: a wrong length must not read past the buffer)"""
+    b = bytes(b)
+    if len(b) != length:
+        raise ValueError(f"expected {length} bytes, got {len(b)}")
+    return (C.c_uint8 * max(1, length)).from_buffer_copy(b or b"\0")
+
+
+def _gsz_dn_counts(L, kind: int, parties: int, degree: int, want: int):
+    deal, outs = C.c_size_t(0), C.c_size_t(0)
+    rc = L.czk_gsz_dn_counts(C.c_int(kind), C.c_size_t(parties), C.c_uint(degree), C.c_size_t(want), C.byref(deal), C.byref(outs))
+    if rc:
+        raise CzkError(rc, "czk_gsz_dn_counts: unknown kind, a degree that leaves nothing to extract, or a count that overflows")
+    return deal.value, outs.value
 
 
 def _ptr(x):
@@ -573,6 +590,32 @@ class Context:
         ok, bad = C.c_uint64(0), C.c_uint64(0)
         self._ck(self._L.czk_gsz_product_check(self._h, C.c_size_t(parties), C.c_uint(degree), _ptr(xs_ptr), _ptr(ys_ptr), _ptr(zs_ptr), C.c_size_t(n),
                                              _ptr(doubles_r_ptr), _ptr(doubles_r2_ptr), _ptr(rands_ptr), C.byref(ok), C.byref(bad)))
+        return bool(ok.value), bad.value
+
+    # ---- the GSZ material made on the device (czk.h; csrc/gsz_dn.hip) -----------------------------------------------------------------------
+    def fr_random(self, key: bytes, nonce: bytes, first: int, n: int, out=None, mem=CZK_MEM_HOST):
+        """czk_fr_random: element i = the ChaCha20 block at (key, nonce, first + i) as a field element -> (n, 4) uint64 Montgomery (host), or `out` (a pointer in `mem`)"""
+        k, nc = _key_bytes(key, 32), _key_bytes(nonce, 12)
+        if mem == CZK_MEM_HOST and out is None:
+            out = np.zeros((n, 4), dtype=np.uint64)
+        self._ck(self._L.czk_fr_random(self._h, k, nc, C.c_uint32(first), C.c_size_t(n), _ptr(out if n else None), C.c_int(mem)))
+        return out
+
+    def gsz_dn_counts(self, kind: int, parties: int, degree: int, want: int):
+        """(deal, outputs): the smallest deal whose deal (parties - degree) outputs reach `want`"""
+        return _gsz_dn_counts(self._L, kind, parties, degree, want)
+
+    def gsz_dn_generate(self, kind: int, parties: int, degree: int, keys, nonce: bytes, deal: int, out_r_ptr, out_r2_ptr=None):
+        """czk_gsz_dn_generate: keys = `parties` x 32 bytes; out_r / out_r2: `parties` device lanes of deal (parties - degree) elements.  Enqueues."""
+        kb = _key_bytes(b"".join(bytes(k) for k in keys) if not isinstance(keys, (bytes, bytearray)) else keys, 32 * parties)
+        self._ck(self._L.czk_gsz_dn_generate(self._h, C.c_int(kind), C.c_size_t(parties), C.c_uint(degree), kb, _key_bytes(nonce, 12), C.c_size_t(deal), _ptr(out_r_ptr),
+                                             _ptr(out_r2_ptr)))
+
+    def gsz_dn_check(self, kind: int, parties: int, degree: int, r_ptr, r2_ptr, outputs: int):
+        """czk_gsz_dn_check -> (ok, opens over their bound); ok = False is a result, not an error.  The last two outputs are sacrificed."""
+        ok, bad = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.czk_gsz_dn_check(self._h, C.c_int(kind), C.c_size_t(parties), C.c_uint(degree), _ptr(r_ptr), _ptr(r2_ptr), C.c_size_t(outputs), C.byref(ok),
+                                          C.byref(bad)))
         return bool(ok.value), bad.value
 
     def share_domain_constants(self, parties: int):
@@ -1104,6 +1147,16 @@ class Net:
         self._ck(self._L.czk_net_recv_from_king(self._h, _ptr(send if nbytes else None), C.c_size_t(nbytes), _ptr(recv if nbytes else None), C.c_int(mem)))
         return recv
 
+    def alltoall(self, send, nbytes: int | None = None, recv=None, mem: int = CZK_MEM_HOST):
+        """send: (world, nbytes), part p goes to party p -> recv (world, nbytes), part p came from party p"""
+        if mem == CZK_MEM_HOST:
+            send = np.ascontiguousarray(send).view(np.uint8).reshape(-1)
+            nbytes = send.size // self.world
+            send = send.reshape(self.world, nbytes)
+            recv = np.zeros((self.world, nbytes), dtype=np.uint8)
+        self._ck(self._L.czk_net_alltoall(self._h, _ptr(send if nbytes else None), C.c_size_t(nbytes), _ptr(recv if nbytes else None), C.c_int(mem)))
+        return recv
+
     def atomic_broadcast(self, x_ptr, n: int, recv_ptr, rand32: bytes | None = None, mem: int = CZK_MEM_DEVICE, tree: bool = False):
         """tree=True: the commitment is czk.h's tree commitment, hashed on the GPU (all ranks must choose alike)"""
         r = (C.c_uint8 * 32).from_buffer_copy(rand32) if rand32 is not None else None
@@ -1178,6 +1231,21 @@ class Net:
         ok, bad = C.c_uint64(0), C.c_uint64(0)
         self._ck(self._L.czk_net_gsz_product_check(self._h, C.c_uint(degree), _ptr(xs_ptr), _ptr(ys_ptr), _ptr(zs_ptr), C.c_size_t(n), _ptr(doubles_r_ptr),
                                                    _ptr(doubles_r2_ptr), _ptr(rands_ptr), C.byref(ok), C.byref(bad)))
+        return bool(ok.value), bad.value
+
+    # ---- the GSZ material with one party per communicator (czk_net_gsz_dn_*, czk.h): this party's key, its ONE lane -----------------------------
+    def gsz_dn_counts(self, kind: int, degree: int, want: int):
+        return _gsz_dn_counts(self._L, kind, self.world, degree, want)
+
+    def gsz_dn_generate(self, kind: int, degree: int, key: bytes, nonce: bytes, deal: int, out_r_ptr, out_r2_ptr=None):
+        """czk_net_gsz_dn_generate: deals under this party's 32-byte key, one all-to-all, extracts its lane of deal (world - degree) outputs"""
+        self._ck(self._L.czk_net_gsz_dn_generate(self._h, C.c_int(kind), C.c_uint(degree), _key_bytes(key, 32), _key_bytes(nonce, 12), C.c_size_t(deal), _ptr(out_r_ptr),
+                                                 _ptr(out_r2_ptr)))
+
+    def gsz_dn_check(self, kind: int, degree: int, r_ptr, r2_ptr, outputs: int):
+        """czk_net_gsz_dn_check -> (ok, opens over their bound); ok is the same on every rank"""
+        ok, bad = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.czk_net_gsz_dn_check(self._h, C.c_int(kind), C.c_uint(degree), _ptr(r_ptr), _ptr(r2_ptr), C.c_size_t(outputs), C.byref(ok), C.byref(bad)))
         return bool(ok.value), bad.value
 
     def fr_send_to_king(self, x_ptr, n: int, gathered_ptr):

@@ -31,7 +31,7 @@ LIB_LAB = os.path.join(HERE, "libczk_hip_lab.so")
 # group operations): out of line too, 14 s instead of 4.5 min of host compilation.
 SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_MUL"]), ("ntt.hip", []), ("ntt_pass.hip", []), ("ntt_mixed.hip", []), ("msm.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_sort.hip", ["-DCZK_NOINLINE_MUL"]),
            ("msm_bases.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_acc_g1.hip", []),
-           ("msm_acc_g2.hip", []), ("msm_red_g2.hip", []), ("msm_heavy_g2.hip", []), ("poly.hip", []), ("share.hip", []), ("share_mul.hip", []), ("gsz_mul.hip", []), ("net.hip", ["-DCZK_NOINLINE_MUL"]),
+           ("msm_acc_g2.hip", []), ("msm_red_g2.hip", []), ("msm_heavy_g2.hip", []), ("poly.hip", []), ("share.hip", []), ("share_mul.hip", []), ("gsz_mul.hip", []), ("gsz_dn.hip", []), ("net.hip", ["-DCZK_NOINLINE_MUL"]),
            ("pairing.hip", ["-DCZK_NOINLINE_MUL"]), ("fixed_base.hip", []), ("point_codec.hip", ["-DCZK_NOINLINE_MUL"]),
            ("point_ops.hip", ["-DCZK_NOINLINE_MUL"]), ("kzg.hip", ["-DCZK_NOINLINE_MUL"]), ("marlin_index.hip", []), ("plonk_layout.hip", []), ("commit_tree.hip", [])]
 # lab library only: never compiled into, nor linked with, the product library

@@ -389,6 +389,17 @@ int gsz_net_check_hadamard(czk_ctx* ctx, GszNetCheck& c, const u64* xs, const u6
 int gsz_net_check_round_send(czk_ctx* ctx, GszNetCheck& c);   // -> c.wire[0, 2)
 int gsz_net_check_round_recv(czk_ctx* ctx, GszNetCheck& c);   // c.king[0, 2), c.opened[0] -> the fold
 int gsz_net_check_final(czk_ctx* ctx, GszNetCheck& c, int step);   // steps 0..3 of the end, see gsz_mul.hip
+// implemented in gsz_dn.hip: what czk_net_gsz_dn_* (net.hip) launches between its exchanges, everything enqueued on ctx->stream
+int gsz_dn_shape(czk_ctx* ctx, const char* what, int kind, size_t parties, unsigned degree, size_t deal);   // the argument rules of czk_gsz_dn_generate
+int gsz_dn_points_launch(czk_ctx* ctx, size_t parties, u64* points);                                        // points[e] = w^e, e < parties
+// send[(j halves + half) deal + b] = this dealer's share of its item b for party j (halves = 2 for doubles, 1 for random shares)
+int gsz_dn_deal_launch(czk_ctx* ctx, int kind, size_t parties, unsigned degree, const uint8_t* key, const uint8_t* nonce, size_t deal, const u64* points, u64* send);
+// recv in the same layout, by dealer -> this party's ONE lane of the deal (parties - degree) outputs
+int gsz_dn_extract_launch(czk_ctx* ctx, int kind, size_t parties, unsigned degree, size_t deal, const u64* points, const u64* recv, u64* out_r, u64* out_r2);
+// the check's local pass: u[half lanes + lane] = r[outputs - 1] + sum_{m < outputs - 2} coin^(m + 1) r[m] (coin: device memory; r2 may be null)
+size_t gsz_dn_combine_ws(czk_ctx* ctx, size_t lanes, size_t outputs);   // workspace, in elements
+int gsz_dn_combine_launch(czk_ctx* ctx, size_t lanes, const u64* r, const u64* r2, size_t stride, size_t outputs, const u64* coin, u64* ws, u64* u);
+int gsz_dn_verdict_launch(czk_ctx* ctx, const u64* opened);             // opened[0] != opened[1] -> ctx->share_cnt[1] = 1
 // implemented in ntt.hip
 // `addend` (lanes x D canonical Fr, not the lanes being transformed) rides on the last pass's store: a coset inverse transform writes
 // (coset_ifft(data) - addend) * *scale, a forward or coset forward transform writes its output + addend (scale unused).  Same values as the pointwise kernels.

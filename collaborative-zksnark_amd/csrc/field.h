@@ -64,6 +64,12 @@ struct FrParams {
                               0xe5dc8593u, 0xa7cc008fu, 0xeff1c939u, 0x011fdae7u};
         return m[i];
     }
+    // 2^252 R2 mod r: with R2 (= 2^256 R) the two constants that take the halves of a 504-bit sample lo + 2^252 hi to Montgomery form (gsz_dn.hip)
+    static CZK_HD u32 r2_252(int i) {
+        constexpr u32 m[8] = {0x90f65455u, 0xd928895cu, 0xaee27169u, 0x8c8f6fffu,
+                              0x062a8971u, 0x434b6937u, 0xfbe77233u, 0x050af751u};
+        return m[i];
+    }
 };
 
 struct FqParams {

@@ -387,13 +387,32 @@ int shm_step_barrier(czk_net* n, bool wrote) {
     return shm_barrier(n);
 }
 
-enum class Op { Broadcast, ToKing, FromKing };
+enum class Op { Broadcast, ToKing, FromKing, AllToAll };
 
 // One exchange in chunk steps of slot_bytes.  Step k uses the slots of parity k: a slot written in step k is read in step k and
 // next written in step k + 2, which lies behind barrier k + 1 -- and a rank arrives there only after its reads of step k completed.
 int shm_exchange(czk_net* n, Op op, const char* send, size_t bytes, char* recv, int mem) {
     CZK_TRY(shm_data(n));
     const int W = n->world, me = n->rank;
+    if (op == Op::AllToAll) {   // a rank's slot carries `world` segments per chunk step, one per destination
+        const size_t seg = (n->slot_bytes / (size_t)W) & ~(size_t)15;
+        if (!seg) return net_err(n, CZK_ERR_SIZE, "czk_net_alltoall: slot_bytes holds less than 16 bytes per destination");
+        CZK_TRY(local_copy(n, recv + (size_t)me * bytes, send + (size_t)me * bytes, bytes, mem));
+        for (size_t off = 0; off < bytes || off == 0; off += seg) {
+            const size_t len = bytes - off < seg ? bytes - off : seg;
+            const uint64_t par = n->seq++;
+            bool wrote = false;
+            if (len)
+                for (int p = 0; p < W; p++)
+                    if (p != me) CZK_TRY(shm_put(n, shm_slot(n, me, par) + (size_t)p * seg, send + (size_t)p * bytes + off, len, mem, &wrote));
+            CZK_TRY(shm_step_barrier(n, wrote));
+            if (len)
+                for (int p = 0; p < W; p++)
+                    if (p != me) CZK_TRY(shm_get(n, recv + (size_t)p * bytes + off, shm_slot(n, p, par) + (size_t)me * seg, len, mem));
+            if (bytes == 0) break;
+        }
+        return CZK_OK;
+    }
     if (op == Op::Broadcast) CZK_TRY(local_copy(n, recv + (size_t)me * bytes, send, bytes, mem));
     if (op == Op::ToKing && me == 0) CZK_TRY(local_copy(n, recv, send, bytes, mem));
     if (op == Op::FromKing && me == 0) CZK_TRY(local_copy(n, recv, send, bytes, mem));
@@ -427,6 +446,18 @@ int rccl_exchange_dev(czk_net* n, Op op, const char* send, size_t bytes, char* r
     if (bytes == 0) return CZK_OK;
     if (op == Op::Broadcast && n->exchange == 0) {
         NET_NCCL(n, R->AllGather(send, recv, bytes, ncclChar, n->comm, st));
+        return CZK_OK;
+    }
+    if (op == Op::AllToAll) {   // world - 1 send / receive pairs, every pair of GPUs on its own xGMI link
+        CZK_TRY(local_copy(n, recv + (size_t)me * bytes, send + (size_t)me * bytes, bytes, CZK_MEM_DEVICE));
+        if (W == 1) return CZK_OK;
+        NET_NCCL(n, R->GroupStart());
+        for (int d = 1; d < W; d++) {
+            const int to = (me + d) % W, from = (me - d + W) % W;
+            NET_NCCL(n, R->Send(send + (size_t)to * bytes, bytes, ncclChar, to, n->comm, st));
+            NET_NCCL(n, R->Recv(recv + (size_t)from * bytes, bytes, ncclChar, from, n->comm, st));
+        }
+        NET_NCCL(n, R->GroupEnd());
         return CZK_OK;
     }
     if (op == Op::Broadcast) {   // p2p: world - 1 concurrent copies of this party's buffer, one per xGMI link
@@ -465,6 +496,7 @@ void op_sizes(const czk_net* n, Op op, size_t bytes, size_t* send_b, size_t* rec
         case Op::Broadcast: *send_b = bytes, *recv_b = bytes * n->world; break;
         case Op::ToKing: *send_b = bytes, *recv_b = king ? bytes * n->world : 0; break;
         case Op::FromKing: *send_b = king ? bytes * n->world : 0, *recv_b = bytes; break;
+        case Op::AllToAll: *send_b = *recv_b = bytes * n->world; break;
     }
 }
 
@@ -509,6 +541,9 @@ void count_stats(czk_net* n, Op op, size_t m) {   // mpc-net/src/multi.rs:148-15
             n->stats[4]++;
             if (n->rank == 0) n->stats[0] += others * (m + 8);
             else n->stats[1] += m;
+            break;
+        case Op::AllToAll:   // bytes only: mpc-net has no such primitive, none of its three exchange counters moves
+            n->stats[0] += others * m, n->stats[1] += others * m;
             break;
     }
 }
@@ -671,6 +706,11 @@ extern "C" int czk_net_send_to_king(czk_net* n, const void* send, size_t bytes, 
 extern "C" int czk_net_recv_from_king(czk_net* n, const void* send, size_t bytes, void* recv, int mem) {
     CZK_TRY(exchange(n, Op::FromKing, send, bytes, recv, mem));
     count_stats(n, Op::FromKing, bytes);
+    return CZK_OK;
+}
+extern "C" int czk_net_alltoall(czk_net* n, const void* send, size_t bytes, void* recv, int mem) {
+    CZK_TRY(exchange(n, Op::AllToAll, send, bytes, recv, mem));
+    count_stats(n, Op::AllToAll, bytes);
     return CZK_OK;
 }
 extern "C" int czk_net_barrier(czk_net* n) {
@@ -1143,5 +1183,58 @@ extern "C" int czk_net_gsz_product_check(czk_net* n, unsigned degree, const uint
     uint64_t failed = 0;
     NET_CTX(n, share_counters_read(ctx, out_bad, &failed));          // the one read-back of the check
     *out_ok = failed ? 0 : 1;
+    return CZK_OK;
+}
+
+// ---- czk_net_gsz_dn_*: the GSZ material dealt and extracted with one party per communicator (kernels in gsz_dn.hip) --------------------------------------
+// The party deals under its OWN key alone; one all-to-all carries its shares out and the others' in; the extraction is local.  No rank sees another's key.
+extern "C" int czk_net_gsz_dn_generate(czk_net* n, int kind, unsigned degree, const uint8_t* key, const uint8_t* nonce, size_t deal, uint64_t* out_r, uint64_t* out_r2) {
+    if (!n) return CZK_ERR_ARG;
+    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_generate needs a communicator created with a context");
+    czk_ctx* ctx = n->ctx;
+    const size_t W = (size_t)n->world;
+    NET_CTX(n, gsz_dn_shape(ctx, "czk_net_gsz_dn_generate", kind, W, degree, deal));
+    if (!deal) return CZK_OK;
+    const bool doubles = kind == CZK_GSZ_DN_DOUBLES;
+    if (!key || !nonce || !out_r || (doubles && !out_r2)) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_generate: null argument");
+    NET_HIP(n, hipSetDevice(ctx->device));
+    const size_t per = (doubles ? 2 : 1) * deal;   // elements per peer
+    StageHold ws(ctx);
+    NET_CTX(n, ws.take((96 + 2 * W * per) * 32));
+    u64 *points = (u64*)ws.b.p, *send = points + 4 * 96, *recv = send + 4 * W * per;
+    NET_CTX(n, gsz_dn_points_launch(ctx, W, points));
+    NET_CTX(n, gsz_dn_deal_launch(ctx, kind, W, degree, key, nonce, deal, points, send));
+    CZK_TRY(czk_net_alltoall(n, send, per * 32, recv, CZK_MEM_DEVICE));
+    NET_CTX(n, gsz_dn_extract_launch(ctx, kind, W, degree, deal, points, recv, out_r, doubles ? out_r2 : nullptr));
+    return CZK_OK;
+}
+
+extern "C" int czk_net_gsz_dn_check(czk_net* n, int kind, unsigned degree, const uint64_t* r, const uint64_t* r2, size_t outputs, uint64_t* out_ok, uint64_t* out_bad) {
+    if (!n) return CZK_ERR_ARG;
+    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check needs a communicator created with a context");
+    if (!out_ok || !out_bad) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check: null result output");
+    *out_ok = *out_bad = 0;
+    czk_ctx* ctx = n->ctx;
+    NET_CTX(n, gsz_dn_shape(ctx, "czk_net_gsz_dn_check", kind, (size_t)n->world, degree, 0));
+    const bool doubles = kind == CZK_GSZ_DN_DOUBLES;
+    if (outputs < 3) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check: fewer than 3 outputs (two are sacrificed)");
+    if (!r || (doubles && !r2)) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check: null argument");
+    if (outputs >> 32) return net_err(n, CZK_ERR_SIZE, "czk_net_gsz_dn_check: more than 2^32 - 1 outputs");
+    NET_HIP(n, hipSetDevice(ctx->device));
+    const size_t cws = gsz_dn_combine_ws(ctx, 1, outputs);
+    StageHold ws(ctx);
+    NET_CTX(n, ws.take((cws + 5) * 32));
+    u64 *u = (u64*)ws.b.p + 4 * cws, *coin = u + 4 * 2, *opened = coin + 4;
+    NET_CTX(n, share_counters(ctx));
+    CZK_TRY(gsz_open_trip(n, r + 4 * (outputs - 2), 1, nullptr, degree, coin, ctx->share_cnt, nullptr));   // the coin: the first sacrificed output, opened
+    NET_CTX(n, gsz_dn_combine_launch(ctx, 1, r, doubles ? r2 : nullptr, outputs, outputs, coin, (u64*)ws.b.p, u));
+    CZK_TRY(gsz_open_trip(n, u, 1, nullptr, degree, opened, ctx->share_cnt, nullptr));
+    if (doubles) {
+        CZK_TRY(gsz_open_trip(n, u + 4, 1, nullptr, 2 * degree, opened + 4, ctx->share_cnt, nullptr));
+        NET_CTX(n, gsz_dn_verdict_launch(ctx, opened));
+    }
+    uint64_t differ = 0;
+    NET_CTX(n, share_counters_read(ctx, out_bad, &differ));   // the one read-back of the check
+    *out_ok = (differ || *out_bad) ? 0 : 1;
     return CZK_OK;
 }

@@ -589,3 +589,29 @@ def gsz_product_check(ctx, degree: int, xs, ys, zs, doubles_r, doubles_r2, rands
     _after_consume(ctx, vecs[0])
     if not ok or bad:
         raise MpcCheckError(f"gsz_product_check of {n} triples: verdict {int(ok)}, {bad} degree violation(s)")
+
+
+# ---- the GSZ material with one process per party (czk_net_gsz_dn_*, include/czk.h): this party deals under its own key ---------------------------------------
+def gsz_dn_generate(ctx, kind: int, degree: int, key: bytes, nonce: bytes, deal: int):
+    """this party's lane of the deal (world - degree) random (kind 1) or double (kind 0) shares: (r, r2), r2 None for random shares.  Every rank passes
+    the same nonce and never the same (key, nonce) twice."""
+    if _NET is None:
+        raise RuntimeError("parallel.gsz_dn_generate runs over a czk_net communicator: call parallel.use_net(parallel.make_net(ctx, 'shm')) first")
+    _, outputs = _NET.gsz_dn_counts(kind, degree, deal * (_NET.world - degree))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    r = torch.empty((outputs, 4), dtype=torch.int64, device=dev)
+    r2 = torch.empty_like(r) if kind == 0 else None
+    _net_in(ctx, r)
+    _NET.gsz_dn_generate(kind, degree, key, nonce, deal, r.data_ptr(), None if r2 is None else r2.data_ptr())
+    return _after_consume(ctx, r), r2
+
+
+def gsz_dn_check(ctx, kind: int, degree: int, r, r2=None) -> None:
+    """the consistency check over this party's lane (the last two outputs are sacrificed); raises MpcCheckError when it fails"""
+    vecs = _gsz_net_vecs("gsz_dn_check", [v for v in (r, r2) if v is not None])
+    for v in vecs:
+        _net_in(ctx, v)
+    ok, bad = _NET.gsz_dn_check(kind, degree, vecs[0].data_ptr(), vecs[1].data_ptr() if len(vecs) > 1 else None, vecs[0].shape[0])
+    _after_consume(ctx, vecs[0])
+    if not ok:
+        raise MpcCheckError(f"gsz_dn_check of {vecs[0].shape[0]} outputs: verdict 0, {bad} degree violation(s)")

@@ -248,7 +248,7 @@ class SharingError(RuntimeError):
 
 class Sharing:
     """The lanes of a GpuBackend as a real sharing: lpp = 1 additive, lpp = 2 SPDZ (lane lpp p = party p's sh, lane lpp p + 1 its mac), `parties`
-    parties, correlated randomness from `source` (DummySource, SeededDealer).  MAC key: the reference's 0 / 1 key (see the module's head).
+    parties, correlated randomness from `source` (DummySource, SeededDealer; DnSource for GSZ).  MAC key: the reference's 0 / 1 key (see the module's head).
     scheme="gsz" (lpp = 1): lane j is party j's Shamir share p(w^j) of degree t = (parties - 1) // 2 (gsz20/mod.rs:94-105); a public value lifts to
     every lane (from_public, :185-187: a degree-0 sharing); `parties` must be a size the share domain exists for (2^a or 3 * 2^a, at most 96)."""
 
@@ -373,6 +373,63 @@ class SeededDealer:
 
     def rands(self, B, n: int):
         return self._shamir(B, self._random(B, n), B.sharing.degree)
+
+
+class DnSource:
+    """GSZ double and random shares made on the device by Damgard-Nielsen dealing and extraction (czk_gsz_dn_generate) and guarded by its consistency
+    check (czk_gsz_dn_check): the `doubles(B, n)` / `rands(B, n)` of Sharing(scheme="gsz").
+
+    keys: one 32-byte ChaCha20 key per party; None draws them from os.urandom at the first call (the library itself never supplies entropy).  The nonce
+    of a call is LE32(kind) || LE64(sequence) and the sequence is bumped at every call, so no (key, nonce, counter) triple is ever used twice by one
+    source -- two sources must not share keys.  A call deals ceil((n + 2) / (parties - t)) items, runs the check (which sacrifices the last two outputs;
+    check=False skips it) and returns the first n elements of every lane.  A failed check raises SharingError.
+
+    WHAT THIS IS.  In this lanes form ONE process holds every party's key: it is a fast dealer, not a secure one -- it knows every value it deals, like
+    SeededDealer.  Security is the property of the net form (czk_net_gsz_dn_generate, parallel.gsz_dn_generate), where every party deals under its own
+    key: no rank learns another's key, t colluding ranks learn nothing about an output, and the guarantee is for semi-honest dealing plus the
+    consistency check (a dealer that cheats is detected, not tolerated).  The shared-memory transports (CZK_NET_SHM, CZK_NET_IPC) expose their
+    mailboxes to every process of the node, so there the parties must trust the node."""
+
+    def __init__(self, keys=None, check: bool = True):
+        self.keys = None if keys is None else [bytes(k) for k in keys]
+        if self.keys is not None and any(len(k) != 32 for k in self.keys):
+            raise ValueError("DnSource: every key is 32 bytes")
+        self.check, self.sequence = bool(check), 0
+
+    def _generated(self, B, kind, r, r2):
+        """the lanes as generated, before the check (a test's cheating dealer perturbs them here)"""
+        return r, r2
+
+    def _make(self, B, kind: int, n: int):
+        import os
+
+        S, bd = B.sharing, B.czk.binding
+        P, d = S.parties, S.degree
+        if self.keys is None:
+            self.keys = [os.urandom(32) for _ in range(P)]
+        if len(self.keys) != P:
+            raise ValueError(f"DnSource: {len(self.keys)} keys for {P} parties")
+        doubles = kind == bd.CZK_GSZ_DN_DOUBLES
+        if n == 0:
+            return B._new(P, 0), (B._new(P, 0) if doubles else None)
+        deal, outputs = B.ctx.gsz_dn_counts(kind, P, d, n + 2)
+        nonce = int(kind).to_bytes(4, "little") + self.sequence.to_bytes(8, "little")
+        self.sequence += 1
+        r, r2 = B._new(P, outputs), (B._new(P, outputs) if doubles else None)
+        B.ctx.gsz_dn_generate(kind, P, d, self.keys, nonce, deal, r.data_ptr(), r2.data_ptr() if doubles else None)
+        r, r2 = self._generated(B, kind, r, r2)
+        if self.check:
+            ok, bad = B.ctx.gsz_dn_check(kind, P, d, r.data_ptr(), r2.data_ptr() if doubles else None, outputs)
+            if not ok:
+                raise SharingError(f"consistency check of {outputs} generated {'double' if doubles else 'random'} shares failed: {bad} degree violation(s)")
+        return r[:, :n].contiguous(), (r2[:, :n].contiguous() if doubles else None)
+
+    def doubles(self, B, n: int):
+        """n double shares (gsz20/mod.rs:395-406): one uniformly random value under a polynomial of degree t and under one of degree 2 t"""
+        return self._make(B, B.czk.binding.CZK_GSZ_DN_DOUBLES, n)
+
+    def rands(self, B, n: int):
+        return self._make(B, B.czk.binding.CZK_GSZ_DN_RANDS, n)[0]
 
 
 def shared_stream_context(czk, device: int = 0):

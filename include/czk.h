@@ -326,6 +326,12 @@ int czk_net_send_to_king(czk_net* net, const void* send, size_t bytes, void* rec
  * king, ignored elsewhere); recv (bytes) receives this party's.  The reference prefixes each message with its u64 length
  * (multi.rs:219-228); here lengths are arguments and only the stats count the 8 bytes. */
 int czk_net_recv_from_king(czk_net* net, const void* send, size_t bytes, void* recv, int mem);
+/* All-to-all (mpc-net has no such primitive; the GSZ material's dealing needs one): send is world x bytes and part p goes to party p; recv is
+ * world x bytes and part p came from party p; the caller's own part is a local copy.  Over CZK_NET_SHM / CZK_NET_IPC a rank's slot carries `world`
+ * segments per chunk step, so the chunk per destination is slot_bytes / world rounded down to 16 bytes (less than 16: CZK_ERR_SIZE); over
+ * CZK_NET_RCCL it is one group of world - 1 send / receive pairs.  Stats: (world - 1) bytes go into out[0] and out[1]; none of the three exchange
+ * counters moves. */
+int czk_net_alltoall(czk_net* net, const void* send, size_t bytes, void* recv, int mem);
 int czk_net_barrier(czk_net* net);
 /* MpcSerNet::atomic_broadcast of one Vec<Fr> (channel.rs:50-75): round 1 broadcasts SHA-256(serialize(x) || 32 random bytes), round 2
  * the vector and the randomness; every receiver re-hashes what the others sent (CZK_ERR_CHECK on a mismatch).  x: n Montgomery Fr
@@ -489,6 +495,60 @@ int czk_net_gsz_share_partial_products(czk_net* net, unsigned degree, const uint
                                        const uint64_t* rands, uint64_t* out, size_t n, uint64_t* out_bad, uint64_t* out_zero);
 int czk_net_gsz_product_check(czk_net* net, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t n,
                               const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad);
+
+/* ---- GSZ material made on the device: a keyed generator of field elements, Damgard-Nielsen dealing and extraction, its consistency check ---- */
+/* czk_fr_random: a keyed stream of field elements.  Element i comes from the ChaCha20 block (RFC 8439 block function, 20 rounds, 32-bit block counter) at
+ * (key, nonce, counter = first + i): lo = bytes 0..31 of the block as a little-endian integer reduced mod 2^252, hi = bytes 32..63 likewise,
+ * value = (lo + 2^252 hi) mod r, written as Montgomery limbs to out (n Fr, `mem`).  r lies between 2^252 and 2^253, so both halves are canonical
+ * as they stand; the 504-bit sample leaves every residue within r / 2^504 < 2^-251 of uniform (statistical distance below r / 2^504).  The library
+ * supplies no entropy: the key is the caller's, and a (key, nonce, counter) triple must never serve twice.  first + n > 2^32 (the counter would
+ * wrap): CZK_ERR_SIZE.  n = 0: CZK_OK, nothing touched.  NULL key / nonce / out with work to do: CZK_ERR_ARG.
+ *
+ * czk_gsz_dn_generate: the preparation gsz20 assumes and the reference stubs out (share/gsz20/mod.rs:383-406 hand every party a one), in the lanes
+ * form: all `parties` dealers' keys are on this GPU (ONE process knows every value: a fast dealer, not a secure one).  P = parties, d = degree,
+ * w = czk_share_domain_constants' group_gen, draws = 1 + d (CZK_GSZ_DN_RANDS) or 1 + 3 d (CZK_GSZ_DN_DOUBLES).
+ *   Dealer i takes element m of its item b from czk_fr_random's stream under keys[i] (32 bytes each) and `nonce` at counter b draws + m: m = 0 is the
+ *   secret s, then c_1 .. c_d, then (doubles) e_1 .. e_2d.  Its share for party j is s + sum_k c_k w^(jk), in the second half s + sum_k e_k w^(jk).
+ *   Output k deal + b, k = 0 .. P - d - 1, is sum_i w^(ik) (dealer i's item b), share-wise.  outputs = deal (P - d).
+ * Row k of the extraction matrix is (w^(ik))_i, so every (P - d)-column minor is a Vandermonde determinant in distinct nodes: the outputs are uniform
+ * and unknown to any d dealers as long as the other P - d dealt honestly.  out_r / out_r2 (DEVICE): P lanes, party-major, `outputs` elements apart --
+ * the layout of doubles_r / doubles_r2 and of rands in czk_gsz_share_*; out_r2 (the same values under degree 2 d) is NULL for CZK_GSZ_DN_RANDS.
+ * tests/gsz_dn_model.py restates the definition; the kernel extracts the coefficients before it evaluates them (fully reduced limbs do not depend on
+ * the order).  The call only enqueues.  czk_gsz_dn_counts: the `deal` that yields at least `want` outputs, and that `outputs`.
+ * 2 d >= P for doubles, d >= P for random shares, an unknown kind: CZK_ERR_ARG.  deal draws > 2^32, no share domain of that size (0, 5, ...),
+ * P > 96: CZK_ERR_SIZE.  deal = 0: CZK_OK, nothing touched.  Workspace: the staging pool (for P other than 3, 4, 6, 8 it grows with the grid).
+ *
+ * czk_gsz_dn_check: the consistency check, which sacrifices the LAST TWO outputs; the first outputs - 2 are the usable ones.  Output outputs - 2's
+ * degree-d half opens at bound d to the coin rho; u = r[outputs - 1] + sum_{m < outputs - 2} rho^(m + 1) r[m] opens at bound d; for doubles the same
+ * combination of r2 opens at bound 2 d and the two opened values must be equal.  *out_bad counts the opens that exceeded their bound (0 .. 3);
+ * *out_ok = 1 when none did and (doubles) the values were equal, else 0 -- a result, not an error.  A batch with one inconsistent sharing passes with
+ * probability at most outputs / r over the coin (a non-zero polynomial of degree < outputs in rho vanishing).  At odd P the bound 2 d = P - 1 is
+ * vacuous -- every P values interpolate -- and the equality of the two opened values is what binds the second half.  Dealers that cheat are detected,
+ * not tolerated: a failed check says that the batch must be thrown away, not who spoiled it.  The coin stays on the device; counts and verdict are
+ * read back once, at the end (the call blocks).  r, r2: as czk_gsz_dn_generate wrote them (r2 ignored for CZK_GSZ_DN_RANDS); not modified.
+ * outputs < 3, NULL arguments, the degree rules above: CZK_ERR_ARG; the size rules above, outputs >= 2^32: CZK_ERR_SIZE. */
+#define CZK_GSZ_DN_DOUBLES 0   /* the same value under degree d and degree 2 d */
+#define CZK_GSZ_DN_RANDS 1     /* degree d only */
+int czk_fr_random(czk_ctx* ctx, const uint8_t* key, const uint8_t* nonce, uint32_t first, size_t n, uint64_t* out, int mem);
+int czk_gsz_dn_counts(int kind, size_t parties, unsigned degree, size_t want, size_t* deal, size_t* outputs);
+int czk_gsz_dn_generate(czk_ctx* ctx, int kind, size_t parties, unsigned degree, const uint8_t* keys, const uint8_t* nonce, size_t deal, uint64_t* out_r,
+                        uint64_t* out_r2);
+int czk_gsz_dn_check(czk_ctx* ctx, int kind, size_t parties, unsigned degree, const uint64_t* r, const uint64_t* r2, size_t outputs, uint64_t* out_ok,
+                     uint64_t* out_bad);
+
+/* The same generation and check with one party per communicator: the party is czk_net_rank(net) of P = czk_net_world(net) parties, deals under its
+ * OWN key (32 bytes) alone and holds ONE lane of `outputs` Fr, CZK_MEM_DEVICE on the communicator's context.  No rank learns another's key; `degree`
+ * colluding ranks learn nothing about an output as long as the other P - degree dealt honestly; the guarantee is for semi-honest dealing plus the
+ * consistency check (a cheating dealer is detected, not tolerated).  The shared-memory transports expose their mailboxes to every process of the node.
+ *   czk_net_gsz_dn_generate   the party's draws evaluated at every party's point, [destination][half][b]; ONE czk_net_alltoall of halves deal 32 bytes per
+ *                             peer (halves = 2 for doubles); the extraction of this party's lane.  Rank j's out_r / out_r2 are lane j of what
+ *                             czk_gsz_dn_generate writes on the same keys (keys[j] = rank j's) and nonce, limb for limb.  Every rank passes the same nonce.
+ *   czk_net_gsz_dn_check      the coin and the combinations open through broadcasts of ONE element each: three for doubles, two for random shares.
+ *                             *out_ok comes out equal on all ranks, and equal to czk_gsz_dn_check's on the lanes; *out_bad counts the opens (every rank
+ *                             checks every bound).
+ * Argument rules: those of the lanes form with parties = the world; a communicator without a context: CZK_ERR_ARG. */
+int czk_net_gsz_dn_generate(czk_net* net, int kind, unsigned degree, const uint8_t* key, const uint8_t* nonce, size_t deal, uint64_t* out_r, uint64_t* out_r2);
+int czk_net_gsz_dn_check(czk_net* net, int kind, unsigned degree, const uint64_t* r, const uint64_t* r2, size_t outputs, uint64_t* out_ok, uint64_t* out_bad);
 
 /* The king's side of king_compute (mpc-algebra/src/channel.rs:77-80; gsz20's degree reduction, share/gsz20/mod.rs:470-500): every
  * party's n Fr to the king, who receives world x n (device, party order) -- czk_net_send_to_king on Fr lanes -- and the way back. */

@@ -137,6 +137,7 @@ extern "C" {
     pub fn czk_net_broadcast(net: *mut czk_net, send: *const c_void, bytes: usize, recv: *mut c_void, mem: c_int) -> c_int;
     pub fn czk_net_send_to_king(net: *mut czk_net, send: *const c_void, bytes: usize, recv: *mut c_void, mem: c_int) -> c_int;
     pub fn czk_net_recv_from_king(net: *mut czk_net, send: *const c_void, bytes: usize, recv: *mut c_void, mem: c_int) -> c_int;
+    pub fn czk_net_alltoall(net: *mut czk_net, send: *const c_void, bytes: usize, recv: *mut c_void, mem: c_int) -> c_int;
     pub fn czk_net_barrier(net: *mut czk_net) -> c_int;
     pub fn czk_net_atomic_broadcast(net: *mut czk_net, x: *const u64, n: usize, recv: *mut u64, rand32: *const u8, mem: c_int) -> c_int;
     pub fn czk_fr_vec_commit(ctx: *mut czk_ctx, a: *const u64, lanes: usize, n: usize, stride: usize, rand32: *const u8, out32: *mut u8, mem: c_int) -> c_int;
@@ -160,6 +161,12 @@ extern "C" {
     pub fn czk_net_gsz_share_batch_inv(net: *mut czk_net, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
     pub fn czk_net_gsz_share_partial_products(net: *mut czk_net, degree: c_uint, x: *const u64, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out: *mut u64, n: usize, out_bad: *mut u64, out_zero: *mut u64) -> c_int;
     pub fn czk_net_gsz_product_check(net: *mut czk_net, degree: c_uint, xs: *const u64, ys: *const u64, zs: *const u64, n: usize, doubles_r: *const u64, doubles_r2: *const u64, rands: *const u64, out_ok: *mut u64, out_bad: *mut u64) -> c_int;
+    pub fn czk_fr_random(ctx: *mut czk_ctx, key: *const u8, nonce: *const u8, first: u32, n: usize, out: *mut u64, mem: c_int) -> c_int;
+    pub fn czk_gsz_dn_counts(kind: c_int, parties: usize, degree: c_uint, want: usize, deal: *mut usize, outputs: *mut usize) -> c_int;
+    pub fn czk_gsz_dn_generate(ctx: *mut czk_ctx, kind: c_int, parties: usize, degree: c_uint, keys: *const u8, nonce: *const u8, deal: usize, out_r: *mut u64, out_r2: *mut u64) -> c_int;
+    pub fn czk_gsz_dn_check(ctx: *mut czk_ctx, kind: c_int, parties: usize, degree: c_uint, r: *const u64, r2: *const u64, outputs: usize, out_ok: *mut u64, out_bad: *mut u64) -> c_int;
+    pub fn czk_net_gsz_dn_generate(net: *mut czk_net, kind: c_int, degree: c_uint, key: *const u8, nonce: *const u8, deal: usize, out_r: *mut u64, out_r2: *mut u64) -> c_int;
+    pub fn czk_net_gsz_dn_check(net: *mut czk_net, kind: c_int, degree: c_uint, r: *const u64, r2: *const u64, outputs: usize, out_ok: *mut u64, out_bad: *mut u64) -> c_int;
     pub fn czk_fr_send_to_king(net: *mut czk_net, x: *const u64, n: usize, gathered: *mut u64) -> c_int;
     pub fn czk_fr_recv_from_king(net: *mut czk_net, parts: *const u64, n: usize, out: *mut u64) -> c_int;
     pub fn czk_gsz_batch_king_compute(net: *mut czk_net, val: *const u64, n: usize, degrees: *const u32, degree: c_uint, out: *mut u64, out_bad: *mut u64) -> c_int;
