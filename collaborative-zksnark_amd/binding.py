@@ -46,7 +46,8 @@ def _share_material_counts(L, op: int, n: int):
 
 
 CZK_GSZ_OP_MUL, CZK_GSZ_OP_INV, CZK_GSZ_OP_PARTIAL_PRODUCTS, CZK_GSZ_OP_PRODUCT_CHECK = 0, 1, 2, 3   # czk_gsz_material_counts
-CZK_GSZ_DN_DOUBLES, CZK_GSZ_DN_RANDS = 0, 1   # czk_gsz_dn_*: the same value under degree d and 2 d / degree d only
+CZK_GSZ_GROUP_OP_MUL, CZK_GSZ_GROUP_OP_PRODUCT_CHECK = 0, 1   # czk_gsz_group_material_counts
+CZK_GSZ_DN_DOUBLES, CZK_GSZ_DN_RANDS = 0, 1  # czk_gsz_dn_*: the same value under degree d and 2 d / degree d only
 
 
 def open_commit_flags(commit) -> int:
@@ -590,6 +591,47 @@ class Context:
         ok, bad = C.c_uint64(0), C.c_uint64(0)
         self._ck(self._L.czk_gsz_product_check(self._h, C.c_size_t(parties), C.c_uint(degree), _ptr(xs_ptr), _ptr(ys_ptr), _ptr(zs_ptr), C.c_size_t(n),
                                              _ptr(doubles_r_ptr), _ptr(doubles_r2_ptr), _ptr(rands_ptr), C.byref(ok), C.byref(bad)))
+        return bool(ok.value), bad.value
+
+    # ---- a shared point times a shared scalar on device lanes: GroupShare::scale and gsz20's group mult (czk.h; csrc/group_share.hip) ------------
+    def gsz_group_material_counts(self, op: int, n: int):
+        """(group doubles, field doubles, random shares) one call of `op` (CZK_GSZ_GROUP_OP_*) over n elements consumes"""
+        g, f, r = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        rc = self._L.czk_gsz_group_material_counts(C.c_int(op), C.c_size_t(n), C.byref(g), C.byref(f), C.byref(r))
+        if rc:
+            raise CzkError(rc, "czk_gsz_group_material_counts: unknown op or a count that overflows")
+        return g.value, f.value, r.value
+
+    def share_group_batch_scale(self, group: int, lpp: int, parties: int, mac_shares, s_ptr, s_inf_ptr, o_ptr, tx_ptr, tx_inf_ptr, ty_ptr, tz_ptr, tz_inf_ptr,
+                                out_ptr, out_inf_ptr, n: int):
+        """czk_share_group_batch_scale: point vectors (s, tx, tz, out) are lpp * parties device lanes of n affine points + as many infinity bytes (an input's
+        may be None), scalar vectors (o, ty) as many lanes of n Montgomery Fr; mac_shares (parties, 4) Montgomery limbs (None for lpp = 1).
+        Points are assumed to lie in the prime-order subgroup.  Returns the number of elements whose MAC checks failed."""
+        ms = None if mac_shares is None else np.ascontiguousarray(mac_shares, np.uint64).reshape(-1, 4)
+        assert ms is None or ms.shape[0] >= parties
+        bad = C.c_uint64(0)
+        self._ck(self._L.czk_share_group_batch_scale(self._h, C.c_int(group), C.c_size_t(lpp), C.c_size_t(parties), _ptr(ms), _ptr(s_ptr), _ptr(s_inf_ptr), _ptr(o_ptr),
+                                                   _ptr(tx_ptr), _ptr(tx_inf_ptr), _ptr(ty_ptr), _ptr(tz_ptr), _ptr(tz_inf_ptr), _ptr(out_ptr), _ptr(out_inf_ptr),
+                                                   C.c_size_t(n), C.byref(bad)))
+        return bad.value
+
+    def gsz_group_batch_mul(self, group: int, parties: int, degree: int, x_ptr, y_ptr, y_inf_ptr, gr_ptr, gr_inf_ptr, gr2_ptr, gr2_inf_ptr, out_ptr, out_inf_ptr,
+                            n: int):
+        """czk_gsz_group_batch_mul: x `parties` device lanes of n Montgomery Fr; y, gr, gr2, out as many lanes of n affine points + infinity bytes (an
+        input's may be None).  Returns the number of elements that exceeded the king's degree bound."""
+        bad = C.c_uint64(0)
+        self._ck(self._L.czk_gsz_group_batch_mul(self._h, C.c_int(group), C.c_size_t(parties), C.c_uint(degree), _ptr(x_ptr), _ptr(y_ptr), _ptr(y_inf_ptr), _ptr(gr_ptr),
+                                               _ptr(gr_inf_ptr), _ptr(gr2_ptr), _ptr(gr2_inf_ptr), _ptr(out_ptr), _ptr(out_inf_ptr), C.c_size_t(n), C.byref(bad)))
+        return bad.value
+
+    def gsz_group_product_check(self, group: int, parties: int, degree: int, xs_ptr, ys_ptr, ys_inf_ptr, zs_ptr, zs_inf_ptr, n: int, gr_ptr, gr_inf_ptr, gr2_ptr,
+                                gr2_inf_ptr, fr_ptr, fr2_ptr, rands_ptr):
+        """czk_gsz_group_product_check over n triples (xs scalars, ys and zs points) -> (ok, degree violations); ok = False is a result, not an error.
+        gr / gr2: group doubles, fr / fr2: field doubles, rands: random shares, as gsz_group_material_counts(CZK_GSZ_GROUP_OP_PRODUCT_CHECK, n) counts them."""
+        ok, bad = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.czk_gsz_group_product_check(self._h, C.c_int(group), C.c_size_t(parties), C.c_uint(degree), _ptr(xs_ptr), _ptr(ys_ptr), _ptr(ys_inf_ptr),
+                                                   _ptr(zs_ptr), _ptr(zs_inf_ptr), C.c_size_t(n), _ptr(gr_ptr), _ptr(gr_inf_ptr), _ptr(gr2_ptr), _ptr(gr2_inf_ptr),
+                                                   _ptr(fr_ptr), _ptr(fr2_ptr), _ptr(rands_ptr), C.byref(ok), C.byref(bad)))
         return bool(ok.value), bad.value
 
     # ---- the GSZ material made on the device (czk.h; csrc/gsz_dn.hip) -----------------------------------------------------------------------

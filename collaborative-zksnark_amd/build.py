@@ -33,7 +33,7 @@ SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_
            ("msm_bases.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_acc_g1.hip", []),
            ("msm_acc_g2.hip", []), ("msm_red_g2.hip", []), ("msm_heavy_g2.hip", []), ("poly.hip", []), ("share.hip", []), ("share_mul.hip", []), ("gsz_mul.hip", []), ("gsz_dn.hip", []), ("net.hip", ["-DCZK_NOINLINE_MUL"]),
            ("pairing.hip", ["-DCZK_NOINLINE_MUL"]), ("fixed_base.hip", []), ("point_codec.hip", ["-DCZK_NOINLINE_MUL"]),
-           ("point_ops.hip", ["-DCZK_NOINLINE_MUL"]), ("kzg.hip", ["-DCZK_NOINLINE_MUL"]), ("marlin_index.hip", []), ("plonk_layout.hip", []), ("commit_tree.hip", [])]
+           ("point_ops.hip", ["-DCZK_NOINLINE_MUL"]), ("group_share.hip", ["-DCZK_NOINLINE_MUL"]), ("kzg.hip", ["-DCZK_NOINLINE_MUL"]), ("marlin_index.hip", []), ("plonk_layout.hip", []), ("commit_tree.hip", [])]
 # lab library only: never compiled into, nor linked with, the product library
 LAB_SOURCES = [(os.path.join("lab", "arith_probe.hip"), []), (os.path.join("lab", "sat_probe.hip"), ["-DCZK_NOINLINE_MUL"])]
 HEADERS = ["field.h", "curve.h", "czk_internal.h", "call.h", "sha256.h", "pow_tables.h", "msm_acc.h", "fq2p.h", "fq2pu.h", "fqu.h", "fru.h", "fru_constants.inc", "ntt_pass.h", "te.h", "te_constants.inc", "tower.h", "pairing_constants.inc",

@@ -3,7 +3,9 @@ C ABI (binding.py).  Mirrors the reference's call sequences, not its protocol lo
 
   Groth16Local   R1CStoQAP::witness_map (mpc-snarks/src/groth/r1cs_to_qap.rs:47-113) + the MSM sequence of create_proof
                  (mpc-snarks/src/groth/prover.rs:66-178), Beaver local half (mpc-algebra/src/share/field.rs:97-127);
-                 create_proof's O(1) group steps and the Proof{a, b, c} share of every lane for public r, s (prover.rs:110-178, 216-232)
+                 create_proof's O(1) group steps and the Proof{a, b, c} share of every lane for public r, s (prover.rs:110-178, 216-232);
+                 create_proof_shared: the same for SHARED r, s, the three products of a shared point and a shared scalar as one device call
+                 (GroupShare::scale, mpc-algebra/src/share/group.rs:70-109; gsz20's group mult and product check, share/gsz20/mod.rs:1112-1349)
 
 Used by bench.py (timed) and tests/ (parity against the checker).  torch provides device memory and streams only.
 """
@@ -483,6 +485,139 @@ class Groth16Local:
             out["a"][ln], out["b"][ln], out["c"][ln] = g_a, g2_b, g_c
         return out
 
+    # ---- create_proof for SHARED r, s: the group-level products (czk_share_group_batch_scale / czk_gsz_group_batch_mul, csrc/group_share.hip) ----
+    def mac_shares(self):
+        """the parties' shares of the MAC key, as ints: the reference's stand-in key, 1 on the king and 0 elsewhere (share/spdz.rs:30-37)"""
+        return [1 if p == 0 else 0 for p in range(self.P)]
+
+    def share_domain_root(self) -> int:
+        wn = self.ctx.share_domain_constants(self.P)["group_gen"]
+        return sum(int(wn[i]) << (64 * i) for i in range(4)) * pow(1 << 256, -1, R_MOD) % R_MOD
+
+    def share_values(self, values, rng, degree=None):
+        """A random sharing of every int in `values` for the scheme in use, in the prover's lane order -> lanes of ints.  Additive (hbc): a random
+        split over the parties.  SPDZ: that, and a random split of key * value on the mac lanes, key = the sum of mac_shares().  GSZ: a random
+        polynomial of degree `degree` (default t) on the share domain, lane j = p(w^j), p(0) = the value.  rng: a random.Random (tests) or
+        random.SystemRandom."""
+        n, P = len(values), self.P
+        out = [[0] * n for _ in range(self.lpp * P)]
+        if self.scheme == "gsz":
+            w, deg = self.share_domain_root(), self.gsz_t if degree is None else degree
+            for i, v in enumerate(values):
+                cs = [v % R_MOD] + [rng.randrange(R_MOD) for _ in range(deg)]
+                for j in range(P):
+                    out[j][i] = sum(c * pow(w, j * k, R_MOD) for k, c in enumerate(cs)) % R_MOD
+            return out
+        key = sum(self.mac_shares()) % R_MOD
+        for i, v in enumerate(values):
+            for m, tot in ((0, v % R_MOD), (1, key * v % R_MOD))[:self.lpp]:
+                parts = [rng.randrange(R_MOD) for _ in range(P - 1)]
+                parts.append((tot - sum(parts)) % R_MOD)
+                for p in range(P):
+                    out[self.lpp * p + m][i] = parts[p]
+        return out
+
+    def share_scalar(self, value: int, rng) -> np.ndarray:
+        """share_values for one scalar -> (L, 4) uint64 Montgomery lanes: what create_proof_shared takes for r and s"""
+        return to_mont_limbs([ln[0] for ln in self.share_values([value], rng)])
+
+    def lift_lanes(self, group, lanes):
+        """lanes of (n, 4) Montgomery scalars, a (L, n, 4) DEVICE tensor -> the lanes of [k] G: ((L, n, 12|24) int64, (L, n) uint8) device tensors --
+        czk_points_mul with stride 0 on the generator, so a share of k becomes that party's share of [k] G"""
+        czk, ctx = self.czk, self.ctx
+        L, n = lanes.shape[0], lanes.shape[1]
+        aw = 12 if group == czk.CZK_G1 else 24
+        gen = torch.from_numpy(ctx.fixed_base_points(group, np.array([[1, 0, 0, 0]], np.uint64))[0].view(np.int64).copy()).cuda()
+        pts = torch.empty((L, n, aw), dtype=torch.int64, device="cuda")
+        inf = torch.empty((L, n), dtype=torch.uint8, device="cuda")
+        ctx.points_mul(group, gen.data_ptr(), lanes.data_ptr(), stride=0, scalar_form=czk.CZK_SCALAR_MONTGOMERY, n=L * n, out=pts.data_ptr(), out_inf=inf.data_ptr(),
+                       mem=czk.CZK_MEM_DEVICE)
+        ctx.sync()                                             # `gen` is read in stream order
+        return pts, inf
+
+    def _products(self, pts, inf):
+        """the three product shares as the device call left them, before the check (a test's cheating party alters them here)"""
+        return pts, inf
+
+    def create_proof_shared(self, res, r_lanes, s_lanes, source):
+        """create_proof (mpc-snarks/src/groth/prover.rs:110-178) for SHARED r, s: (L, 4) Montgomery lanes in this prover's lane order (share_scalar).
+        The linear steps stay on the host as in create_proof: scale_pub_group of delta by the r / s lanes (:125, :142, :154), calculate_coeff with
+        `shift` on the lanes that take public addends, the final additions.  The three products of a shared point and a shared scalar --
+        [r] delta * s (:110-114), g_a * s (:135), g1_b * r (:156) -- are ONE call with n = 3: czk_share_group_batch_scale on group triples from
+        `source` (additive, SPDZ) or czk_gsz_group_batch_mul on its group doubles (GSZ).  Under GSZ czk_gsz_group_product_check then runs over the
+        three triples.  A failed MAC check, degree bound or verdict raises polyvm.SharingError before anything is returned.
+        source: DummyGroupSource, SeededGroupDealer or (GSZ) DnGroupSource.  All parties' lanes must be on this GPU.  Returns what create_proof does."""
+        from .polyvm import SharingError
+        czk, ctx = self.czk, self.ctx
+        G1, G2, M = czk.CZK_G1, czk.CZK_G2, czk.CZK_MEM_DEVICE
+        assert len(self.local) == self.P and self.base_split is None, "the lanes form: every party's lanes on this GPU"
+        res = self.expand_results(res)
+        pk, L = self.pk, self.lanes
+        r_lanes, s_lanes = np.ascontiguousarray(r_lanes, np.uint64).reshape(L, 4), np.ascontiguousarray(s_lanes, np.uint64).reshape(L, 4)
+        MONT = czk.CZK_SCALAR_MONTGOMERY
+        one = to_mont_limbs_fq(1)
+        delta_g1 = np.concatenate([pk["delta_g1"], one]).astype(np.uint64)
+        delta_g2 = np.concatenate([pk["delta_g2"], one, np.zeros(6, np.uint64)]).astype(np.uint64)
+
+        def coeff(group, initial, el_aff, el_inf, acc, vk_param, king):                          # :216-232 on one lane; `initial` is that lane's share
+            if not king:
+                return ctx.jac_add(group, initial, acc)
+            out = ctx.jac_add_mixed(group, initial, el_aff, el_inf)
+            out = ctx.jac_add(group, out, acc)
+            return ctx.jac_add_mixed(group, out, vk_param, False)
+        inf1, inf2 = np.zeros(12, np.uint64), np.zeros(24, np.uint64)
+        g_a, g2_b = np.zeros((L, 18), np.uint64), np.zeros((L, 36), np.uint64)
+        pts, inf = np.zeros((L, 3, 12), np.uint64), np.zeros((L, 3), np.uint8)                   # the shared points of the three products
+        for ln in range(L):
+            king = ln in self.king_lanes
+            r_g1 = ctx.jac_scalar_mul(G1, delta_g1, r_lanes[ln], MONT)                           # scale_pub_group(delta, r) (:125)
+            s_g1 = ctx.jac_scalar_mul(G1, delta_g1, s_lanes[ln], MONT)                           # :142
+            s_g2 = ctx.jac_scalar_mul(G2, delta_g2, s_lanes[ln], MONT)                           # :154
+            g_a[ln] = coeff(G1, r_g1, pk["a_query0"], False, res["a"][ln], pk["alpha_g1"], king)
+            g1_b = coeff(G1, s_g1, inf1, True, res["b_g1"][ln], pk["beta_g1"], king)
+            g2_b[ln] = coeff(G2, s_g2, inf2, True, res["b_g2"][ln], pk["beta_g2"], king)
+            for k, jac in enumerate((r_g1, g_a[ln], g1_b)):
+                aff, ai = ctx.jac_to_affine(G1, jac)
+                pts[ln, k], inf[ln, k] = aff[0], ai[0]
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64) if a.dtype == np.uint64 else np.ascontiguousarray(a)).cuda()   # noqa: E731
+        sc = dev(np.stack([s_lanes, s_lanes, r_lanes], axis=1))                                  # (L, 3, 4): times s, times s, times r
+        d_pts, d_inf = dev(pts), dev(inf)
+        out = torch.empty((L, 3, 12), dtype=torch.int64, device="cuda")
+        out_inf = torch.empty((L, 3), dtype=torch.uint8, device="cuda")
+        if self.scheme == "gsz":
+            gr, gr_inf, gr2, gr2_inf = source.group_doubles(self, G1, 3)
+            bad = ctx.gsz_group_batch_mul(G1, self.P, self.gsz_t, sc.data_ptr(), d_pts.data_ptr(), d_inf.data_ptr(), gr.data_ptr(), gr_inf.data_ptr(), gr2.data_ptr(),
+                                          gr2_inf.data_ptr(), out.data_ptr(), out_inf.data_ptr(), 3)
+            if bad:
+                raise SharingError(f"group products: {bad} element(s) exceeded the king's degree bound")
+            out, out_inf = self._products(out, out_inf)
+            gd, fd, nr = ctx.gsz_group_material_counts(czk.binding.CZK_GSZ_GROUP_OP_PRODUCT_CHECK, 3)
+            gr, gr_inf, gr2, gr2_inf = source.group_doubles(self, G1, gd)
+            fr, fr2 = source.field_doubles(self, fd)
+            rands = source.rands(self, nr)
+            ok, bad = ctx.gsz_group_product_check(G1, self.P, self.gsz_t, sc.data_ptr(), d_pts.data_ptr(), d_inf.data_ptr(), out.data_ptr(), out_inf.data_ptr(), 3,
+                                                  gr.data_ptr(), gr_inf.data_ptr(), gr2.data_ptr(), gr2_inf.data_ptr(), fr.data_ptr(), fr2.data_ptr(), rands.data_ptr())
+            if not ok or bad:
+                raise SharingError(f"group product check failed: verdict {ok}, {bad} degree violation(s)")
+        else:
+            tx, tx_inf, ty, tz, tz_inf = source.group_triples(self, G1, 3)
+            bad = ctx.share_group_batch_scale(G1, self.lpp, self.P, to_mont_limbs(self.mac_shares()) if self.lpp == 2 else None, d_pts.data_ptr(), d_inf.data_ptr(),
+                                              sc.data_ptr(), tx.data_ptr(), tx_inf.data_ptr(), ty.data_ptr(), tz.data_ptr(), tz_inf.data_ptr(), out.data_ptr(),
+                                              out_inf.data_ptr(), 3)
+            if bad:
+                raise SharingError(f"group products: the MAC check failed for {bad} element(s)")
+            out, out_inf = self._products(out, out_inf)
+        prod, prod_inf = out.cpu().numpy().view(np.uint64), out_inf.cpu().numpy()
+        proof = {"a": g_a, "b": g2_b, "c": np.zeros((L, 18), np.uint64)}
+        zero = ctx.jac_scalar_mul(G1, delta_g1, np.zeros(4, np.uint64))
+        for ln in range(L):
+            rsd, s_g_a, r_g1_b = (ctx.jac_add_mixed(G1, zero, prod[ln, k], bool(prod_inf[ln, k])) for k in range(3))
+            g_c = ctx.jac_add(G1, s_g_a, r_g1_b)                                                 # :163-164
+            g_c = ctx.jac_add(G1, g_c, ctx.jac_neg(G1, rsd))                                     # g_c -= &r_s_delta_g1: every lane subtracts its share
+            g_c = ctx.jac_add(G1, g_c, res["l"][ln])
+            proof["c"][ln] = ctx.jac_add(G1, g_c, res["h"][ln])
+        return proof
+
     def msm_scalars(self):
         """{query: device tensor of the Montgomery scalars its MSM consumed (lanes, n, 4)}; `h` is the LAST proof's."""
         return {"h": self.ab, "l": self.wit, "a": self.asg, "b_g1": self.asg, "b_g2": self.asg}
@@ -517,3 +652,114 @@ class Groth16Local:
 
     def g1_mixed_additions_per_step(self, windows: int):
         return windows * self.lanes * sum(hi - lo for lo, hi in (self.base_range(n) for n in (self.D - 1, self.N, self.N + 1, self.N + 1)))
+
+
+# ---- correlated randomness for create_proof_shared: one small interface, everything as DEVICE tensors in the prover's lane order ----------------
+#   group_triples(prover, group, n) -> (tx, tx_inf, ty, tz, tz_inf)   additive / SPDZ: tx, tz (L, n, 12|24) points, ty (L, n, 4) scalars, tz = [ty] tx
+#   group_doubles(prover, group, n) -> (gr, gr_inf, gr2, gr2_inf)     GSZ: one random point under degree t (gr) and under 2 t (gr2) in the exponent
+#   field_doubles(prover, n)        -> (fr, fr2)                      GSZ: the field's double shares, (P, n, 4)
+#   rands(prover, n)                -> (P, n, 4)                      GSZ: random shares of degree t
+def _dev(a):
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
+
+
+def _infinity(group_aw: int, L: int, n: int):
+    """L lanes of n points at infinity: flag 1 with the coordinates (0, 1), as the library writes them"""
+    pts = np.zeros((L, n, group_aw), np.uint64)
+    pts[:, :, group_aw // 2:group_aw // 2 + 6] = to_mont_limbs_fq(1)
+    return _dev(pts), _dev(np.ones((L, n), np.uint8))
+
+
+class DummyGroupSource:
+    """The reference's stubs.  DummyGroupTripleSource (mpc-algebra/src/wire/group.rs:37-56): a zero point, a one on the king, a zero point.  gsz20's
+    double_rand for groups (share/gsz20/mod.rs:1008-1034): zero points; its field stubs (:383-406): a one on every party."""
+
+    def group_triples(self, p, group, n):
+        aw = 12 if group == p.czk.CZK_G1 else 24
+        x, x_inf = _infinity(aw, p.lanes, n)
+        y = np.zeros((p.lanes, n, 4), np.uint64)
+        for ln in p.king_lanes:                                    # from_add_shared(1) on the king: its sh, and its mac under the stand-in key 1
+            y[ln] = to_mont_limbs([1])[0]
+        return x, x_inf, _dev(y), x, x_inf
+
+    def group_doubles(self, p, group, n):
+        z, z_inf = _infinity(12 if group == p.czk.CZK_G1 else 24, p.lanes, n)
+        return z, z_inf, z, z_inf
+
+    def field_doubles(self, p, n):
+        one = _dev(np.tile(to_mont_limbs([1])[0], (p.lanes, n, 1)))
+        return one, one
+
+    def rands(self, p, n):
+        return _dev(np.tile(to_mont_limbs([1])[0], (p.lanes, n, 1)))
+
+
+class SeededGroupDealer:
+    """Random group triples, group doubles, field doubles and random shares from a seed: the values are drawn and shared on the host (the prover's
+    share_values) and lifted onto the generator on the device.  INSECURE BY CONSTRUCTION: this one process knows every value it deals, discrete logs
+    included.  For tests and measurements only."""
+
+    def __init__(self, seed: int):
+        import random
+        self.rng = random.Random(seed)
+
+    def _scalars(self, p, values, degree=None):
+        return _dev(np.stack([to_mont_limbs(ln) for ln in p.share_values(values, self.rng, degree)]))
+
+    def group_triples(self, p, group, n):
+        x, y = [self.rng.randrange(R_MOD) for _ in range(n)], [self.rng.randrange(R_MOD) for _ in range(n)]
+        tx, tx_inf = p.lift_lanes(group, self._scalars(p, x))
+        tz, tz_inf = p.lift_lanes(group, self._scalars(p, [a * b % R_MOD for a, b in zip(x, y)]))
+        return tx, tx_inf, self._scalars(p, y), tz, tz_inf
+
+    def group_doubles(self, p, group, n):
+        v = [self.rng.randrange(R_MOD) for _ in range(n)]
+        return p.lift_lanes(group, self._scalars(p, v, p.gsz_t)) + p.lift_lanes(group, self._scalars(p, v, 2 * p.gsz_t))
+
+    def field_doubles(self, p, n):
+        v = [self.rng.randrange(R_MOD) for _ in range(n)]
+        return self._scalars(p, v, p.gsz_t), self._scalars(p, v, 2 * p.gsz_t)
+
+    def rands(self, p, n):
+        return self._scalars(p, [self.rng.randrange(1, R_MOD) for _ in range(n)], p.gsz_t)
+
+
+class DnGroupSource:
+    """GSZ material made on the device: czk_gsz_dn_generate's field doubles and random shares (Damgard-Nielsen dealing and extraction, guarded by
+    czk_gsz_dn_check), the group doubles being field doubles lifted with czk_points_mul on the generator: [r_j] G is party j's share of [r] G, under
+    the same two polynomials in the exponent.  keys: one 32-byte key per party (None: os.urandom at the first call); the nonce of a call is
+    LE32(kind) || LE64(sequence), the sequence bumped at every call.  In this lanes form ONE process holds every key: a fast dealer, not a secure one
+    (polyvm.DnSource says what the net form guarantees)."""
+
+    def __init__(self, keys=None, check: bool = True):
+        self.keys, self.check, self.sequence = None if keys is None else [bytes(k) for k in keys], bool(check), 0
+
+    def _make(self, p, kind, n):
+        import os
+        from .polyvm import SharingError
+        ctx, P, d = p.ctx, p.P, p.gsz_t
+        if self.keys is None:
+            self.keys = [os.urandom(32) for _ in range(P)]
+        doubles = kind == p.czk.binding.CZK_GSZ_DN_DOUBLES
+        deal, outputs = ctx.gsz_dn_counts(kind, P, d, n + 2)
+        nonce = int(kind).to_bytes(4, "little") + self.sequence.to_bytes(8, "little")
+        self.sequence += 1
+        r = torch.empty((P, outputs, 4), dtype=torch.int64, device="cuda")
+        r2 = torch.empty_like(r) if doubles else None
+        ctx.gsz_dn_generate(kind, P, d, self.keys, nonce, deal, r.data_ptr(), r2.data_ptr() if doubles else None)
+        if self.check:
+            ok, bad = ctx.gsz_dn_check(kind, P, d, r.data_ptr(), r2.data_ptr() if doubles else None, outputs)
+            if not ok:
+                raise SharingError(f"consistency check of {outputs} generated shares failed: {bad} degree violation(s)")
+        return r[:, :n].contiguous(), (r2[:, :n].contiguous() if doubles else None)
+
+    def field_doubles(self, p, n):
+        return self._make(p, p.czk.binding.CZK_GSZ_DN_DOUBLES, n)
+
+    def group_doubles(self, p, group, n):
+        r, r2 = self.field_doubles(p, n)
+        return p.lift_lanes(group, r) + p.lift_lanes(group, r2)
+
+    def rands(self, p, n):
+        return self._make(p, p.czk.binding.CZK_GSZ_DN_RANDS, n)[0]

@@ -496,6 +496,67 @@ int czk_net_gsz_share_partial_products(czk_net* net, unsigned degree, const uint
 int czk_net_gsz_product_check(czk_net* net, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t n,
                               const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad);
 
+/* ---- products of a SHARED point and a SHARED scalar (mpc-algebra/src/share/group.rs, share/gsz20/mod.rs) ------------------------------------ */
+/* GroupShare::scale (group.rs:70-109, with the SPDZ forms of share/spdz.rs:385-446) and gsz20's group mult (share/gsz20/mod.rs:1112-1130): what a
+ * prover needs to multiply a shared point by a shared scalar (mpc-snarks/src/groth/prover.rs:110-114, :135, :156).  Lanes form only: every party's
+ * lanes on this GPU, in czk_share_batch_mul's resp. czk_gsz_share_batch_mul's lane order.  All arrays are CZK_MEM_DEVICE on the context's GPU.
+ *   a point vector    L lanes of n affine Montgomery points (12 u64 each for CZK_G1, 24 for CZK_G2), lanes n points apart, plus L n infinity bytes in
+ *                     the same order.  An input's infinity array may be NULL: no point of it is infinity.  Outputs: infinity is flag 1 with (0, 1).
+ *   a scalar vector   L lanes of n Montgomery Fr, lanes n elements apart.
+ * SUBGROUP ASSUMPTION: every point is assumed to lie in the prime-order subgroup (they are shares of MSM results under a checked key); the calls do
+ * not check it.  Under it scalars may be combined mod r before they multiply a point, and the calls do so; every algebraically equal formulation
+ * gives the same affine limbs.
+ *
+ * czk_share_group_batch_scale: lpp = 1 additive shares, lpp = 2 SPDZ shares (lane 2 p = party p's sh, lane 2 p + 1 = its mac); mac_shares: one
+ * Montgomery Fr per party, HOST, any key (NULL allowed for lpp = 1).  s: the shared points, o: the shared scalars; (tx, ty, tz): n group triples,
+ * tx and tz points, ty scalars, tz = [ty] tx.  With sx = open(s + tx) (the sum of the sh lanes) and oy = open(o + ty):
+ *     out_l = tz_l - [oy] tx_l + [k_l oy - ty_l] sx      k_l = 1 on the king's sh lane (lane 0), mac_share_j on party j's mac lane, 0 elsewhere
+ * which is out = z - scale_pub_group(sx, y) - x oy, shifted by [oy] sx (group.rs:90-94).  The lanes of out open to [open(o)] open(s).
+ * *out_bad (host): the elements where a MAC check fails: sum_j ([mac_share_j] sx - mac_j(s + x)) is not infinity, or sum_j (mac_share_j oy -
+ * mac_j(o + y)) is not 0.  Always 0 for lpp = 1: additive shares carry nothing that could catch a changed share.
+ * One kernel, one thread per (lane, element) -- each computes its output as ONE joint double-and-add chain -- plus one thread per element for the
+ * MAC checks in the same launch; then the shared batch normalisation; one read-back of the count (the call blocks).
+ *
+ * czk_gsz_group_batch_mul: `parties` GSZ lanes (party j's lane is the value at w^j); x: shared scalars of degree `degree` d, y: shared points of
+ * degree d; (gr, gr2): n group double shares, the SAME random point under a polynomial of degree d (gr) and one of degree 2 d (gr2) in the exponent.
+ *     D_j = [x_j] y_j + gr2_j;   V = [1 / P] sum_j D_j  (the king's inverse DFT in the exponent, coefficient 0);   out_j = V - gr_j
+ * *out_bad (host): the elements where sum_j [w^(-j k)] D_j is not infinity for some k in (2 d, P): the king's degree bound.
+ * The transform is the field version's (czk_fr_gsz_open); the reference's group open_degree_vec (:1048-1080) multiplies shares[i] where the
+ * transform needs shares[j], which only works for its constant stand-in shares.  The inverse DFT's scalars go into the parties' chains
+ * ([x_j / P] y_j + [1 / P] gr2_j, and one more chain per (party, high coefficient)), so the call is one chain deep: two kernels, the normalisation,
+ * one read-back.  czk_gsz_group_material_counts(CZK_GSZ_GROUP_OP_MUL, n): n group doubles, no field doubles, no random shares.
+ * czk_share_group_batch_scale consumes n group triples.
+ *
+ * czk_gsz_group_product_check: hadamard_check -> ip_check -> ip_compress / ip_compute for group triples (:1132-1349) over the n triples (xs_i, ys_i,
+ * zs_i), xs scalars, ys and zs points: x_i <- rho^i x_i and ip = sum_i [rho^i] zs_i per lane; R = ceil(log2 n) halving rounds (an odd length reads a
+ * zero scalar and an infinite point past its end), each with ip_l = sum [xl] Yl and ip3 = sum [2 xr - xl](2 Yr - Yl) through the king at bound 2 d,
+ * the round's coin c, ip_r = ip - ip_l, the parabola [f_1] ip_l + [f_2] ip_r + [f_3] ip3 (:1253-1273) and the fold x <- (xr - xl) c + (2 xl - xr),
+ * Y <- [c](Yr - Yl) + (2 Yl - Yr); the end is :1317-1328: two field mults, two group mults, three opens and the verdict [x] y == z.
+ * *out_ok = 1 when it holds, 0 when not (a result, not an error); *out_bad: the opens whose polynomial exceeded its bound (the king's, 2 d, and plain
+ * opens, d), over the whole call.  Degrees follow the TRUE degrees, as for czk_gsz_product_check.  Coins stay on the device; counts and verdict are
+ * read back once, at the end (the call blocks); 3 R + 2 kernel launches, none separated by a host synchronisation.  xs, ys, zs are not modified.
+ * Material, consumed in the reference's order (czk_gsz_group_material_counts(CZK_GSZ_GROUP_OP_PRODUCT_CHECK, n) = (2 R + 2, 2, R + 3); 0, 0, 0 for n = 0):
+ *   gr / gr2    group doubles, lanes 2 R + 2 points apart: ip_l and ip3 per round, then mult(yr, y), mult(ip_r, ip)
+ *   fr / fr2    field doubles (as doubles_r / doubles_r2 of czk_gsz_share_*), lanes 2 elements apart: mult(xr, yr), mult(x, xr)
+ *   rands       random shares of degree d, lanes R + 3 apart: the hadamard coin, a coin per round, xr, yr
+ * n = 0: CZK_OK, *out_ok = 1.  n >= 2^32: CZK_ERR_SIZE.
+ *
+ * n = 0 (or parties = 0 for czk_share_group_batch_scale): CZK_OK, nothing touched but *out_bad.  NULL ctx / out_bad, a bad group, lpp not 1 or 2,
+ * more than 32 parties, NULL vectors with work to do: CZK_ERR_ARG.  No share domain of that size (0, 5, ...), more than 96 GSZ parties, more
+ * outputs than one launch covers (2^36 threads): CZK_ERR_SIZE.  out / out_inf must not overlap an input.  Workspace: the staging pool. */
+#define CZK_GSZ_GROUP_OP_MUL 0
+#define CZK_GSZ_GROUP_OP_PRODUCT_CHECK 1
+int czk_gsz_group_material_counts(int op, size_t n, size_t* group_doubles, size_t* field_doubles, size_t* rands);
+int czk_gsz_group_product_check(czk_ctx* ctx, int group, size_t parties, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint8_t* ys_inf,
+                                const uint64_t* zs, const uint8_t* zs_inf, size_t n, const uint64_t* gr, const uint8_t* gr_inf, const uint64_t* gr2,
+                                const uint8_t* gr2_inf, const uint64_t* fr, const uint64_t* fr2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad);
+int czk_share_group_batch_scale(czk_ctx* ctx, int group, size_t lpp, size_t parties, const uint64_t* mac_shares, const uint64_t* s, const uint8_t* s_inf,
+                                const uint64_t* o, const uint64_t* tx, const uint8_t* tx_inf, const uint64_t* ty, const uint64_t* tz, const uint8_t* tz_inf,
+                                uint64_t* out, uint8_t* out_inf, size_t n, uint64_t* out_bad);
+int czk_gsz_group_batch_mul(czk_ctx* ctx, int group, size_t parties, unsigned degree, const uint64_t* x, const uint64_t* y, const uint8_t* y_inf,
+                            const uint64_t* gr, const uint8_t* gr_inf, const uint64_t* gr2, const uint8_t* gr2_inf, uint64_t* out, uint8_t* out_inf, size_t n,
+                            uint64_t* out_bad);
+
 /* ---- GSZ material made on the device: a keyed generator of field elements, Damgard-Nielsen dealing and extraction, its consistency check ---- */
 /* czk_fr_random: a keyed stream of field elements.  Element i comes from the ChaCha20 block (RFC 8439 block function, 20 rounds, 32-bit block counter) at
  * (key, nonce, counter = first + i): lo = bytes 0..31 of the block as a little-endian integer reduced mod 2^252, hi = bytes 32..63 likewise,
