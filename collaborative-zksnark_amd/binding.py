@@ -260,6 +260,43 @@ class Context:
                                              C.c_int(CZK_MEM_HOST)))
         return out
 
+    def lab_msm_sort(self, c: int, scalars, size: int | None = None, split: bool = False, one_pass: bool = False,
+                     scalar_form: int = CZK_SCALAR_CANONICAL, inf=None, nb: int | None = None, dims_only: bool = False):
+        """czk_lab_msm_sort (csrc/lab/msm_sort_probe.hip, lab library only): the digit sort of one MSM call on its own.  scalars: (lanes,
+        n_scalars, 4) u64, of which the first `size` of each lane count; c: the window width (0 with split: the width a table-free call of
+        `size` pairs gets); inf: the table set's infinity flags, (Wd, nb) bytes -- (nb,) with split -- or None; nb: points per window
+        (default: size).  Returns the dimensions the product's own plan code derives (c, Wd, W, lanes = bucket sets, B, total, n_parts,
+        part_shift, cap) and, unless dims_only, the arrays: digits and sorted (lanes, total), counts, offsets and perm (lanes, B); `sorted`
+        holds 0xFFFFFFFF where the sort wrote nothing.  Raises unless the context was opened with lab=True."""
+        if not self._lab:
+            raise RuntimeError("lab_msm_sort needs Context(lab=True): libczk_hip.so does not export czk_lab_msm_sort")
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64)
+        if sc.ndim != 3 or sc.shape[2] != 4:
+            raise ValueError(f"scalars must have the shape (lanes, n_scalars, 4), got {sc.shape}")
+        lanes, n_scalars = sc.shape[0], sc.shape[1]
+        size = n_scalars if size is None else int(size)
+        nb = size if nb is None else int(nb)
+        dims = np.zeros(9, dtype=np.uint64)
+
+        def call(inf_arr, outs):
+            self._ck(self._L.czk_lab_msm_sort(self._h, C.c_uint(c), C.c_int(int(split)), C.c_int(int(one_pass)), _ptr(sc), C.c_size_t(n_scalars),
+                                              C.c_size_t(lanes), C.c_size_t(size), C.c_int(scalar_form), _ptr(inf_arr), C.c_size_t(nb), _ptr(dims),
+                                              *[_ptr(o) for o in outs]))
+
+        call(None, [None] * 5)
+        out = dict(zip(("c", "Wd", "W", "lanes", "B", "total", "n_parts", "part_shift", "cap"), (int(v) for v in dims)))
+        if dims_only:
+            return out
+        if inf is not None:
+            inf = np.ascontiguousarray(inf, dtype=np.uint8)
+            if inf.shape != ((nb,) if split else (out["Wd"], nb)):
+                raise ValueError(f"inf must have the shape (Wd, nb) -- (nb,) with split -- got {inf.shape}")
+        arrs = [np.zeros((out["lanes"], max(1, out[k])), dtype=np.uint32) for k in ("total", "total", "B", "B", "B")]
+        call(inf, arrs)
+        for name, a, k in zip(("digits", "sorted", "counts", "offsets", "perm"), arrs, ("total", "total", "B", "B", "B")):
+            out[name] = a[:, :out[k]]
+        return out
+
     def close(self):
         if self._h:
             self._L.czk_ctx_destroy(self._h)

@@ -475,6 +475,74 @@ struct MsmSortBufs {   // per lane: digits, sorted, ranks (the partitioned sort'
     u32 *digits, *sorted, *ranks, *part_counts, *part_cursor, *part_base, *counts, *offsets, *perm, *chist, *tile_sums;
     uint16_t* part_lb;
 };
+// The sort's dimensions of a call of `size` pairs and `lanes` scalar vectors at window width c (msm.hip msm_plan; the lab's sort probe): reads d.size, writes
+// c, Wd, W, split, real_lanes, lanes, B, total, n_tiles, lds_per_block, n_parts, part_shift and one_pass.  Wd: the digit windows of the table set in use (table-free
+// keys: of the width).  long_calls: the rule below applies (msm_plan: not under the lab's batched-affine record builders, whose partitions are 1024 buckets).
+inline void msm_sort_dims(MsmSortDims& d, unsigned c, unsigned Wd, bool split, size_t lanes, bool long_calls, bool one_pass, size_t lds_per_block) {
+    d.c = c;
+    d.split = split;   // no tables: the width follows the call, every digit window is a lane of its own with one bucket set (see the head of msm.hip)
+    d.Wd = Wd;
+    d.W = split ? 1 : Wd;
+    d.real_lanes = lanes;
+    d.lanes = split ? lanes * Wd : lanes;
+    d.B = (size_t)1 << (c - 1);
+    d.total = (size_t)d.W * d.size;
+    d.n_tiles = (d.B + SCAN_TILE - 1) / SCAN_TILE;
+    d.lds_per_block = lds_per_block;
+    // k_part_sort stages a partition's placement in LDS when it fits (~36 k entries on gfx950): long calls get more, smaller partitions (a partition is
+    // the set of buckets with equal LOW index bits, so any power of two up to MAX_PARTS works; the 2^21-point h query: 1024 partitions of 27 k entries).
+    // Not for table-free keys (choose_c_split keeps Wd * n_parts <= MAX_PARTS).
+    d.n_parts = (unsigned)((d.B + PART_BUCKETS - 1) >> PART_LOG);   // B is a power of two; c <= 22, so at most 2^21 / 1024 = MAX_PARTS
+    if (!split && long_calls)
+        while (d.n_parts < MAX_PARTS && d.n_parts < d.B && d.total / d.n_parts > 30000) d.n_parts <<= 1;
+    for (d.part_shift = 0; (1u << d.part_shift) < d.n_parts;) d.part_shift++;
+    d.one_pass = !split && one_pass;   // the one-pass sort runs under the option only
+}
+// k_part_sort's dynamic LDS: counters + scan scratch + a staging area -- up to the device's per-workgroup limit (gfx950: 160 KiB -> 36 k entries) for long calls, but no larger than
+// a partition can need (twice the mean + slack; a partition beyond the area places directly): short calls have a few hundred entries per partition, and a 160 KiB
+// request would pin one workgroup per CU and block LDS for the kernels of the other contexts on the GPU.  part_sort_cap: the entries the staging area holds.
+constexpr size_t PSORT_FIXED_LDS = (2 * PART_BUCKETS + PSORT_THREADS) * 4;
+inline size_t part_sort_lds(const MsmSortDims& d) {
+    const size_t fixed = PSORT_FIXED_LDS;
+    const size_t limit = d.lds_per_block > fixed + 4096 ? d.lds_per_block : fixed + 4096;
+    size_t want = 2 * (d.total / d.n_parts) + 1024;
+    if (want > d.total) want = d.total;
+    size_t lds = fixed + (want * 4 > 4096 ? want * 4 : 4096);
+    return lds > limit ? limit : lds;
+}
+inline u32 part_sort_cap(const MsmSortDims& d) { return (u32)((part_sort_lds(d) - PSORT_FIXED_LDS) / 4); }
+// A workspace handed out piece by piece, each piece 256-byte aligned
+struct Bump {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t count) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = (T*)(base + off);
+        off += count * sizeof(T);
+        return p;
+    }
+};
+// The sort's arrays, carved from a workspace of msm_sort_bytes(d) bytes.  The order and the alignment are fixed by the sizes alone.
+inline size_t msm_sort_bytes(const MsmSortDims& d) {
+    return d.lanes * (d.total * (4 * 3 + 2) + d.B * 4 * 4 + CNT_BINS * 4 + (size_t)d.n_parts * 12 + 64) + (1 << 16);
+}
+inline void msm_sort_carve(const MsmSortDims& d, char* ws, MsmSortBufs& s) {
+    const size_t lanes = d.lanes, B = d.B;
+    Bump bs{ws};
+    s.digits = bs.take<u32>(lanes * d.total);
+    s.sorted = bs.take<u32>(lanes * d.total);
+    s.ranks = bs.take<u32>(lanes * d.total);
+    s.part_lb = bs.take<uint16_t>(lanes * d.total);
+    s.part_counts = bs.take<u32>(lanes * d.n_parts);
+    s.part_cursor = bs.take<u32>(lanes * d.n_parts);
+    s.part_base = bs.take<u32>(lanes * (d.n_parts + 1));
+    s.counts = bs.take<u32>(lanes * B);
+    s.offsets = bs.take<u32>(lanes * B);
+    s.perm = bs.take<u32>(lanes * B);
+    s.chist = bs.take<u32>(lanes * CNT_BINS);
+    s.tile_sums = bs.take<u32>(lanes * d.n_tiles);
+}
 // Enqueues on `st`: digits -> sorted entries with per-bucket counts / offsets -> buckets in descending-population order (perm).
 hipError_t msm_sort_enqueue(hipStream_t st, const MsmSortDims& d, const MsmSortBufs& s);
 // implemented in point_ops.hip: czk_points_add / _mul / _sum over DEVICE buffers (flags may be null = none infinite; a stride of 0 repeats one point;

@@ -34,18 +34,6 @@
 
 namespace czk {
 
-struct Bump {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = (T*)(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 constexpr unsigned MSM_L = 8, MSM_LOG_L = 3;   // bucket reduction: buckets per chunk of a level
 
 // Everything a call decides before it touches a stream (msm_plan), the options included: the stages branch on these fields.  The head is the sort's view of
@@ -81,29 +69,15 @@ static int msm_plan(czk_ctx* ctx, const czk_bases* b, const u64* scalars, size_t
     p.XW = p.g1 ? GT<Fq>::XW : GT<Fq2>::XW;
     p.size = b->n < n_scalars ? b->n : n_scalars;
     CZK_TRY(pick_tables(ctx, b, p.size, &p.tv, true));
-    p.split = b->split;   // no tables: the width follows the call, every digit window is a lane of its own with one bucket set (see the head of the file)
-    p.c = p.split ? msm_width_for(b, p.size) : p.tv.c;
-    p.Wd = p.split ? msm_num_windows(p.c) : p.tv.W;
-    p.W = p.split ? 1 : p.Wd;
+    // no tables (b->split): the width follows the call, every digit window is a lane of its own with one bucket set (see the head of the file)
     p.nb = p.tv.cover;
-    p.real_lanes = lanes;
-    p.lanes = p.split ? lanes * p.Wd : lanes;
+    // (the long-call partition rule: not under the lab's batched-affine record builders, whose partitions are 1024 buckets)
+    const unsigned c = b->split ? msm_width_for(b, p.size) : p.tv.c;
+    msm_sort_dims(p, c, b->split ? msm_num_windows(c) : p.tv.W, b->split, lanes, ctx->msm_affine_rounds == 0, ctx->msm_sort_onepass, ctx->lds_per_block);
     if (p.lanes > 65535) return set_err(ctx, CZK_ERR_SIZE, "too many MSM lanes");
-    p.B = (size_t)1 << (p.c - 1);
     if ((size_t)p.W * p.nb >= ((size_t)1 << 31)) return set_err(ctx, CZK_ERR_SIZE, "W * n_bases exceeds the 31-bit point index");
-    p.total = (size_t)p.W * p.size;
     p.lvl0 = (p.B + MSM_L - 1) / MSM_L;
-    p.n_tiles = (p.B + SCAN_TILE - 1) / SCAN_TILE;
-    p.lds_per_block = ctx->lds_per_block;
-    // k_part_sort stages a partition's placement in LDS when it fits (~36 k entries on gfx950): long calls get more, smaller partitions (a partition is
-    // the set of buckets with equal LOW index bits, so any power of two up to MAX_PARTS works; the 2^21-point h query: 1024 partitions of 27 k entries).
-    // Not for table-free keys (choose_c_split keeps Wd * n_parts <= MAX_PARTS) nor the lab's batched-affine record builders (1024-bucket partitions).
-    p.n_parts = (unsigned)((p.B + PART_BUCKETS - 1) >> PART_LOG);   // B is a power of two; c <= 22, so at most 2^21 / 1024 = MAX_PARTS
-    if (!p.split && ctx->msm_affine_rounds == 0)
-        while (p.n_parts < MAX_PARTS && p.n_parts < p.B && p.total / p.n_parts > 30000) p.n_parts <<= 1;
-    for (p.part_shift = 0; (1u << p.part_shift) < p.n_parts;) p.part_shift++;
-    p.one_pass = !p.split && ctx->msm_sort_onepass;   // the one-pass sort runs under the option only
-    p.need_sort = p.lanes * (p.total * (4 * 3 + 2) + p.B * 4 * 4 + CNT_BINS * 4 + (size_t)p.n_parts * 12 + 64) + (1 << 16);
+    p.need_sort = msm_sort_bytes(p);
     p.heavy_cap = (u32)(p.lanes * p.total / 256 + 64);
     p.need_red = p.lanes * (p.B * p.XW * 8 + 4 * p.lvl0 * p.XW * 8 + p.JW * 8 + p.B + (size_t)12 * 513 * p.XW * 8) + (size_t)p.heavy_cap * (p.XW * 8 + 32) + (1 << 17);
     p.out_bytes = p.lanes * p.JW * 8;
@@ -150,19 +124,7 @@ static int msm_grow(czk_ctx* ctx, const MsmSlot& slot, const MsmPlan& p) {
 static void msm_carve(const MsmPlan& p, const MsmSlot& slot, const MsmSlot& src, MsmBufs& w) {
     const size_t lanes = p.lanes, B = p.B;
     MsmSortBufs& s = w.sort;
-    Bump bs{(char*)src.ws_sort.p};
-    s.digits = bs.take<u32>(lanes * p.total);
-    s.sorted = bs.take<u32>(lanes * p.total);
-    s.ranks = bs.take<u32>(lanes * p.total);
-    s.part_lb = bs.take<uint16_t>(lanes * p.total);
-    s.part_counts = bs.take<u32>(lanes * p.n_parts);
-    s.part_cursor = bs.take<u32>(lanes * p.n_parts);
-    s.part_base = bs.take<u32>(lanes * (p.n_parts + 1));
-    s.counts = bs.take<u32>(lanes * B);
-    s.offsets = bs.take<u32>(lanes * B);
-    s.perm = bs.take<u32>(lanes * B);
-    s.chist = bs.take<u32>(lanes * CNT_BINS);
-    s.tile_sums = bs.take<u32>(lanes * p.n_tiles);
+    msm_sort_carve(p, (char*)src.ws_sort.p, s);
     Bump br{(char*)slot.ws_red.p};
     w.buckets = br.take<u64>(lanes * B * p.XW);
     for (int i = 0; i < 4; i++) w.lv[i] = br.take<u64>(lanes * p.lvl0 * p.XW);

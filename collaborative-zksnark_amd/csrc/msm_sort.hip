@@ -7,7 +7,7 @@ namespace czk {
 // ------------------------------------------------------------------------------------------------
 // digit extraction + counting sort
 // ------------------------------------------------------------------------------------------------
-// Signed digit of window w of the canonical scalar s: 0 (skip) or |d| | sign<<31, d in [-2^(cw-1), 2^(cw-1)]; `carry` runs from window to window.
+// Signed digit of window w of the canonical scalar s: 0 (skip) or |d| | sign<<31, d in (-2^(cw-1), 2^(cw-1)] (a window value of exactly 2^(cw-1) stays positive); `carry` runs from window to window.
 __device__ __forceinline__ u32 msm_recode_digit(const Fr& s, unsigned c, unsigned W_hi, unsigned w, u32& carry, uint8_t base_is_inf) {
     const unsigned bit = msm_win_bit(c, W_hi, w), cw = msm_win_width(c, W_hi, w);
     const u32 half = 1u << (cw - 1);
@@ -418,16 +418,8 @@ hipError_t msm_sort_enqueue(hipStream_t st, const MsmSortDims& d, const MsmSortB
             else if ((n_parts == 1024 || n_parts == 512) && part_scatter_lds(512, n_parts) <= d.lds_per_block) launch_part_scatter<512>(st, d, s);
             else launch_part_scatter<256>(st, d, s);
         }
-        // dynamic LDS: counters + scan scratch + a staging area -- up to the device's per-workgroup limit (gfx950: 160 KiB -> 36 k entries) for long calls, but no larger than
-        // a partition can need (twice the mean + slack; a partition beyond the area places directly): short calls have a few hundred entries per partition, and a 160 KiB
-        // request would pin one workgroup per CU and block LDS for the kernels of the other contexts on the GPU
-        const size_t fixed = (2 * PART_BUCKETS + PSORT_THREADS) * 4;
-        const size_t limit = d.lds_per_block > fixed + 4096 ? d.lds_per_block : fixed + 4096;
-        size_t want = 2 * (total / n_parts) + 1024;
-        if (want > total) want = total;
-        size_t lds = fixed + (want * 4 > 4096 ? want * 4 : 4096);
-        if (lds > limit) lds = limit;
-        const u32 cap = (u32)((lds - fixed) / 4);
+        const size_t lds = part_sort_lds(d);   // (czk_internal.h: the staging area's size)
+        const u32 cap = part_sort_cap(d);
         hipLaunchKernelGGL(k_part_sort, dim3(n_parts, lanes), dim3(PSORT_THREADS), lds, st, s.ranks, s.part_lb, s.part_base, n_parts, d.part_shift, total, B, s.sorted,
                            s.offsets, s.counts, cap);
     }
