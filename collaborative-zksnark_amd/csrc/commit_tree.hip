@@ -1,5 +1,5 @@
 // commit_tree.hip -- czk_fr_vec_commit: the "czk tree commitment v1" of include/czk.h, a SHA-256 tree over the canonical bytes of Fr vectors, hashed on
-// the GPU where the vectors live.  The commit-then-open round of the SPDZ open (net.hip czk_net_atomic_broadcast_tree) is its user.
+// the GPU where the vectors live.  The commit-then-open round of the SPDZ open (net_rounds.hip czk_net_atomic_broadcast_tree) is its user.
 //
 //   leaf_i = SHA256(TAG_LEAF || bytes of a[i E .. min(n, (i + 1) E)))            k_commit_level<true>:  one thread per (lane, leaf)
 //   node_j = SHA256(TAG_NODE || up to F digests of the level below)              k_commit_level<false>: one thread per (lane, node), one launch per level

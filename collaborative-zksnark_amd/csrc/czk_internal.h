@@ -351,7 +351,7 @@ int upload_pageable(czk_ctx* ctx, void* dev, const void* host, size_t bytes);
 int download_pageable(czk_ctx* ctx, void* host, const void* dev, size_t bytes);
 // implemented in commit_tree.hip: the tree commitments (czk.h "czk tree commitment v1") of `lanes` DEVICE vectors; rand32 / out32: lanes x 32 bytes, host.  Blocking.
 int commit_tree_device(czk_ctx* ctx, const u64* a, size_t lanes, size_t n, size_t stride, const uint8_t* rand32, uint8_t* out32);
-// implemented in share_mul.hip: the kernels of the shared-value protocols that the one-party-per-communicator forms (net.hip) launch between their opens.
+// implemented in share_mul.hip: the kernels of the shared-value protocols that the one-party-per-communicator forms (net_rounds.hip) launch between their opens.
 // A ShareVec is `lanes` vectors `lane_stride` elements apart; elem_stride 0 repeats each lane's first element (partial_products' `vec![m[0]; n]`).
 struct ShareVec {
     const u64* p;
@@ -371,10 +371,10 @@ int share_scale_launch(czk_ctx* ctx, unsigned lanes, ShareVec c, const u64* k, c
 int gsz_open_table(czk_ctx* ctx, size_t parties);
 // czk_fr_gsz_open's launch without its read-back: violations add to the device counter `bad` (ctx->share_cnt for the protocols that read back once)
 int gsz_open_enqueue(czk_ctx* ctx, const u64* shares, size_t parties, size_t n, const uint32_t* degrees, unsigned degree, u64* out_value, unsigned long long* bad);
-// implemented in gsz_mul.hip: the party side of the one-party-per-communicator GSZ calls (net.hip), one lane, everything enqueued on ctx->stream.
+// implemented in gsz_mul.hip: the party side of the one-party-per-communicator GSZ calls (net_rounds.hip), one lane, everything enqueued on ctx->stream.
 int gsz_net_mask_launch(czk_ctx* ctx, ShareVec x, ShareVec y, const u64* r2, u64* d, size_t n);   // d = x y + r2: what goes to the king
 int gsz_net_unmask_launch(czk_ctx* ctx, const u64* v, const u64* r, u64* out, size_t n);          // out = v - r: the king's answer made a share
-// One party's product check between its exchanges.  net.hip moves c.wire to the king, his answer to c.king, opened values to c.opened and broadcasts c.blind.
+// One party's product check between its exchanges.  net_rounds.hip moves c.wire to the king, his answer to c.king, opened values to c.opened and broadcasts c.blind.
 struct GszNetCheck {
     static constexpr size_t SLOT = 4;   // elements per wire buffer (at most 3 travel at once)
     const u64 *dr, *dr2, *rands;
@@ -389,7 +389,7 @@ int gsz_net_check_hadamard(czk_ctx* ctx, GszNetCheck& c, const u64* xs, const u6
 int gsz_net_check_round_send(czk_ctx* ctx, GszNetCheck& c);   // -> c.wire[0, 2)
 int gsz_net_check_round_recv(czk_ctx* ctx, GszNetCheck& c);   // c.king[0, 2), c.opened[0] -> the fold
 int gsz_net_check_final(czk_ctx* ctx, GszNetCheck& c, int step);   // steps 0..3 of the end, see gsz_mul.hip
-// implemented in gsz_dn.hip: what czk_net_gsz_dn_* (net.hip) launches between its exchanges, everything enqueued on ctx->stream
+// implemented in gsz_dn.hip: what czk_net_gsz_dn_* (net_rounds.hip) launches between its exchanges, everything enqueued on ctx->stream
 int gsz_dn_shape(czk_ctx* ctx, const char* what, int kind, size_t parties, unsigned degree, size_t deal);   // the argument rules of czk_gsz_dn_generate
 int gsz_dn_points_launch(czk_ctx* ctx, size_t parties, u64* points);                                        // points[e] = w^e, e < parties
 // send[(j halves + half) deal + b] = this dealer's share of its item b for party j (halves = 2 for doubles, 1 for random shares)

@@ -13,7 +13,7 @@
 //   the consistency check: k_gsz_dn_gather (the sacrificed output -> the coin's open), the per-byte power tables of the coin read from device memory
 //     (pow_tables.h's layout), k_gsz_dn_fold (block partials of sum_m coin^(m + 1) r[m], both halves in one pass), k_gsz_dn_finish (one block: the
 //     combination per lane), k_gsz_open on the combinations (share.hip, without its read-back) and k_gsz_dn_verdict.  One read-back, at the end.
-//   one party per communicator (czk_net_gsz_dn_*, host code in net.hip): the generation cut where the shares cross the wire -- k_gsz_dn_deal (this
+//   one party per communicator (czk_net_gsz_dn_*, host code in net_rounds.hip): the generation cut where the shares cross the wire -- k_gsz_dn_deal (this
 //     party's draws evaluated at every party's point, [destination][half][b]) before the all-to-all, k_gsz_dn_extract (this party's ONE lane) after it;
 //     the check's local pass (gsz_dn_combine_launch) on one lane, its three opens through broadcasts.
 // No scratch in any kernel here (profiles/gsz_dn_resource_usage.txt); LDS only for the block reductions.
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void k_gsz_dn(DnArgs a) {
     }
 }
 
-// ---- one party per communicator (czk_net_gsz_dn_*, host code in net.hip): the same generation cut where the shares cross the wire ---------------------
+// ---- one party per communicator (czk_net_gsz_dn_*, host code in net_rounds.hip): the same generation cut where the shares cross the wire ---------------------
 // Before the all-to-all: this party's item b evaluated at every party's point, send[(j halves + half) deal + b] = its share for party j.  The draws are
 // recomputed per destination: nothing is kept but the Horner accumulator.
 __global__ __launch_bounds__(256) void k_gsz_dn_deal(DnKey key, DnNonce nonce, const u64* points, unsigned P, unsigned d, unsigned halves, unsigned draws, size_t deal, u64* send) {

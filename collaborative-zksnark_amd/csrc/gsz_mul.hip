@@ -13,7 +13,7 @@
 //   powers of the hadamard coin: per-byte power tables as in pow_tables.h, but built by a kernel that READS the coin from device memory (the host
 //     never sees it before the final read-back).  A scan would need its own passes over n; a square-and-multiply per thread costs ~ 60 multiplies
 //     against the 2 parties multiplies of an element's real work.  The tables are 1024 elements and every r^i is at most three multiplies.
-//   one party per communicator (czk_net_gsz_*, host code in net.hip): the same protocols on ONE lane, the kernels cut where values cross the wire:
+//   one party per communicator (czk_net_gsz_*, host code in net_rounds.hip): the same protocols on ONE lane, the kernels cut where values cross the wire:
 //     k_gsz_net_mask (d = x y + r2, to the king) and k_gsz_net_unmask (out = v - r, from his answer) for the products; for the check the one-lane
 //     instantiations of k_gsz_hadamard / k_gsz_ip / k_gsz_fold and the single-block k_gsz_net_round_send / _round_recv / _final_send / _final_mid /
 //     _verdict in place of k_gsz_round / k_gsz_final.  The king's side is k_gsz_open (share.hip) on the gathered elements.
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void k_gsz_final(GszRoundArgs a, unsigned long
     }
 }
 
-// ---- one party per communicator (czk_net_gsz_*, host code in net.hip): this party's ONE lane, the kernels split at the wire ---------------------
+// ---- one party per communicator (czk_net_gsz_*, host code in net_rounds.hip): this party's ONE lane, the kernels split at the wire ---------------------
 // what a party sends to the king in a batch_mult: d = x y + r2 (:570-577)
 __global__ __launch_bounds__(256) void k_gsz_net_mask(ShareVec x, ShareVec y, const u64* r2, u64* d, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)

@@ -3,7 +3,7 @@
 //
 // This header is program text for TWO translation units, because build.py compiles field.h in two forms:
 //   arith_probe.hip   the hot kernels' form (the Montgomery multiply inlined at every call site)
-//   sat_probe.hip     -DCZK_NOINLINE_MUL, the form pairing.hip / point_codec.hip / msm.hip / lanes.hip / net.hip are built with
+//   sat_probe.hip     -DCZK_NOINLINE_MUL, the form pairing.hip / point_codec.hip / msm.hip / lanes.hip / net.hip / net_rounds.hip are built with
 // Each includes it inside its own anonymous namespace (inside namespace czk), so the functors and kernels have internal linkage and the
 // two forms never meet at link time.  The Fq6 / Fq12 probes exist in the no-inline form only (#ifdef CZK_NOINLINE_MUL below): that
 // is the only form the tower is ever compiled in.

@@ -1,5 +1,5 @@
 // sat_probe.hip -- LAB BUILD ONLY (build.py LAB_SOURCES, with -DCZK_NOINLINE_MUL): the saturated field.h / tower.h / curve.h probes in the form
-// pairing.hip, point_codec.hip, msm.hip, lanes.hip and net.hip are built with -- the Montgomery multiply a real function.  The same
+// pairing.hip, point_codec.hip, msm.hip, lanes.hip, net.hip and net_rounds.hip are built with -- the Montgomery multiply a real function.  The same
 // probes with the multiply inlined are compiled in arith_probe.hip, whose czk_lab_arith_probe dispatches here.
 #ifndef CZK_NOINLINE_MUL
 #error "sat_probe.hip is the -DCZK_NOINLINE_MUL form of the probes"

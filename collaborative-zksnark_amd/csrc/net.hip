@@ -1,18 +1,10 @@
-// net.hip -- czk_net_*: the transport of the MPC opens behind the C ABI, and the reference's batch opens
-// as single calls on device lanes.  Host code only (the kernels it launches live in share.hip / share_mul.hip / ntt.hip).
+// net.hip -- czk_net_*: the communicator, the transport of the MPC opens behind the C ABI.  Host code only, no kernel of its
+// own; the rounds built on it (commit-then-open, the batch opens, the shared-value protocols) are net_rounds.hip, through net.h.
 //
 //   reference                                                            here
 //   MpcMultiNet::broadcast          mpc-net/src/multi.rs:145-173          czk_net_broadcast       (RCCL: ncclAllGather | grouped ncclSend / ncclRecv)
 //   MpcMultiNet::send_to_king       mpc-net/src/multi.rs:175-210          czk_net_send_to_king    (RCCL: grouped ncclSend -> king's ncclRecv)
 //   MpcMultiNet::recv_from_king     mpc-net/src/multi.rs:211-242          czk_net_recv_from_king
-//   MpcSerNet::atomic_broadcast     mpc-algebra/src/channel.rs:50-75      czk_net_atomic_broadcast
-//   SpdzFieldShare::batch_open      mpc-algebra/src/share/spdz.rs:166-185 czk_spdz_batch_open
-//   AdditiveFieldShare::batch_open  mpc-algebra/src/share/add.rs:256-259  czk_add_batch_open
-//   GszFieldShare::batch_open       share/gsz20/mod.rs:286-300, 440-466   czk_gsz_batch_open
-//   gsz20::batch_king_compute       share/gsz20/mod.rs:494-527            czk_gsz_batch_king_compute
-//   FieldShare::batch_mul / batch_inv / partial_products  share/field.rs:97-182   czk_net_share_batch_mul / _batch_inv / _partial_products
-//   gsz20 batch_mult / batch_inv / partial_products / hadamard_check  share/gsz20/mod.rs:325-366, :559-808   czk_net_gsz_share_* / czk_net_gsz_product_check
-//   Vec<Fr> wire format             algebra/serialize/src/lib.rs:220-229  czk_fr_vec_serialize / _deserialize
 //
 // Two transports (include/czk.h): RCCL for one party per GPU -- every exchange is enqueued on the context's stream, so the kernels that
 // produce a share lane, the exchange and the kernels that consume the gathered lanes are ordered by the stream itself, no host
@@ -21,7 +13,6 @@
 // on a one-GPU box.  RCCL is resolved with dlopen at the first RCCL communicator: libczk_hip.so does not link against it.
 #include <dlfcn.h>
 #include <fcntl.h>
-#include <rccl/rccl.h>   // types and prototypes only
 #include <sched.h>
 #include <sys/mman.h>
 #include <sys/random.h>
@@ -31,12 +22,10 @@
 
 #include <cstring>
 
-#include "czk_internal.h"
-#include "sha256.h"
+#include "net.h"
 
 using namespace czk;
 
-// (SHA-256, the reference's CommitHash of mpc-algebra/src/channel.rs:92: sha256.h)
 namespace {
 double now_ms() {
     timespec ts;
@@ -91,9 +80,15 @@ Rccl* rccl() {
     });
     return &r;
 }
+#define NET_NCCL(n, call)                                                                                 \
+    do {                                                                                                  \
+        ncclResult_t e__ = (call);                                                                        \
+        if (e__ != ncclSuccess) return net_err((n), CZK_ERR_NET, std::string(#call) + ": " + rccl()->GetErrorString(e__)); \
+    } while (0)
+}  // namespace
 
 // ---- SHM control block (lives in the shared segment; every field is an address-free lock-free atomic on x86-64) ------------------
-struct ShmHeader {
+struct czk::ShmHeader {   // (net.h points to it; nothing outside this file looks inside)
     std::atomic<uint64_t> magic;
     std::atomic<uint32_t> world;
     std::atomic<uint32_t> reserved;  // (keeps the layout of the control block)
@@ -103,61 +98,8 @@ struct ShmHeader {
     std::atomic<uint64_t> slot_bytes;   // published by rank 0 when it creates the data segment
 };
 constexpr uint64_t SHM_MAGIC = 0x314e4b5a43ull;   // "CZKN1"
-}  // namespace
 
-struct czk_net {
-    czk_ctx* ctx = nullptr;
-    int transport = 0, rank = 0, world = 1;
-    std::string err;
-    long exchange = 0;            // 0 ring, 1 p2p
-    long timeout_ms = 120000;
-    uint64_t stats[5] = {0, 0, 0, 0, 0};
-    // RCCL
-    ncclComm_t comm = nullptr;
-    // SHM
-    std::string shm_name;
-    ShmHeader* hdr = nullptr;
-    char* slots = nullptr;        // world x 2 x slot_bytes
-    size_t slot_bytes = (size_t)16 << 20, data_bytes = 0;
-    bool data_pinned = false;
-    // IPC (the SHM control block + one device mailbox per rank, mapped into every peer with hipIpc: staging never leaves device memory)
-    char* mailbox = nullptr;                 // this rank's 2 x slot_bytes, device memory
-    std::vector<char*> peer_mail;            // every rank's mailbox as this process sees it (own entry = mailbox)
-    // lab build, IPC transport created WITHOUT a context: a dry run of the mailbox hand-over on a box without GPUs (tests/test_net.py) -- every rank's "device
-    // mailbox" is a POSIX segment of its own, its 64-byte handle names the owner's rank and device (= rank: every peer is on another device), and the order
-    // allocate -> publish handle -> barrier -> open every peer's handle -> barrier -> exchanges by slot parity is the code the hipIpc path runs
-    bool ipc_dry = false;
-    size_t dry_mail_bytes = 0;
-    bool shm_like() const { return transport == CZK_NET_SHM || transport == CZK_NET_IPC; }
-    uint64_t seq = 0;             // chunk steps so far: parity of the slot in use
-    bool reads_in_flight = false;
-    // scratch on the context's GPU
-    DeviceBuf gather, dx, small;
-};
-
-namespace {
-int net_err(czk_net* n, int code, const std::string& msg) {
-    if (n) n->err = msg;
-    return code;
-}
-#define NET_HIP(n, call)                                                                                  \
-    do {                                                                                                  \
-        hipError_t e__ = (call);                                                                          \
-        if (e__ != hipSuccess) return net_err((n), CZK_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-#define NET_NCCL(n, call)                                                                                 \
-    do {                                                                                                  \
-        ncclResult_t e__ = (call);                                                                        \
-        if (e__ != ncclSuccess) return net_err((n), CZK_ERR_NET, std::string(#call) + ": " + rccl()->GetErrorString(e__)); \
-    } while (0)
-// an error of a czk_* call on the communicator's context becomes the communicator's error too
-#define NET_CTX(n, expr)                                                      \
-    do {                                                                      \
-        int rc__ = (expr);                                                    \
-        if (rc__ != CZK_OK) return net_err((n), rc__, czk_last_error((n)->ctx)); \
-    } while (0)
-
-int net_buf(czk_net* n, DeviceBuf& b, size_t bytes) {
+int czk::net_buf(czk_net* n, DeviceBuf& b, size_t bytes) {
     if (b.bytes >= bytes) return CZK_OK;
     if (b.p) {
         NET_HIP(n, hipStreamSynchronize(n->ctx->stream));   // earlier exchanges may still read the old allocation
@@ -169,6 +111,7 @@ int net_buf(czk_net* n, DeviceBuf& b, size_t bytes) {
     return CZK_OK;
 }
 
+namespace {
 // ---- SHM transport -------------------------------------------------------------------------------------------------------------------
 int shm_barrier(czk_net* n) {
     ShmHeader* h = n->hdr;
@@ -232,24 +175,35 @@ int shm_map(czk_net* n, const std::string& name, size_t bytes, bool create, void
     return CZK_OK;
 }
 
+// The rendezvous on a named segment whose size follows from the agreed slot_bytes, up to the point where this rank has it mapped: rank 0 publishes its
+// slot_bytes and creates the segment, a barrier, the others adopt slot_bytes and map it.  A rank that fails raises the abort flag before it returns: its peers
+// leave their barrier at once instead of after timeout_ms.  The second barrier (everybody has it mapped) and rank 0's unlink are the caller's.
+int shm_rendezvous(czk_net* n, const std::string& name, size_t (*bytes_of)(const czk_net*), void** out) {
+    auto map = [&](bool create) {
+        const int rc = shm_map(n, name, bytes_of(n), create, out);
+        if (rc != CZK_OK) n->hdr->abort.store(1, std::memory_order_release);
+        return rc;
+    };
+    if (n->rank == 0) {
+        n->hdr->slot_bytes.store(n->slot_bytes, std::memory_order_release);
+        CZK_TRY(map(true));
+    }
+    CZK_TRY(shm_barrier(n));   // rank 0 has created the segment and published its slot size
+    if (n->rank != 0) {
+        n->slot_bytes = (size_t)n->hdr->slot_bytes.load(std::memory_order_acquire);
+        CZK_TRY(map(false));
+    }
+    return CZK_OK;
+}
+
 // IPC transport: every rank allocates its mailbox on its GPU, publishes the hipIpc handle through a small shared segment and maps the others'
 int ipc_data(czk_net* n) {
     if (!n->peer_mail.empty()) return CZK_OK;
     const std::string name = n->shm_name + ".h";
-    const size_t hb = (size_t)n->world * sizeof(hipIpcMemHandle_t);
-    if (n->rank == 0) n->hdr->slot_bytes.store(n->slot_bytes, std::memory_order_release);
+    const auto table_bytes = [](const czk_net* c) { return (size_t)c->world * sizeof(hipIpcMemHandle_t); };
+    const size_t hb = table_bytes(n);
     void* p = nullptr;
-    int rc = CZK_OK;
-    if (n->rank == 0) rc = shm_map(n, name, hb, true, &p);
-    if (rc != CZK_OK) n->hdr->abort.store(1, std::memory_order_release);
-    CZK_TRY(rc);
-    CZK_TRY(shm_barrier(n));
-    if (n->rank != 0) {
-        n->slot_bytes = (size_t)n->hdr->slot_bytes.load(std::memory_order_acquire);
-        rc = shm_map(n, name, hb, false, &p);
-        if (rc != CZK_OK) n->hdr->abort.store(1, std::memory_order_release);
-        CZK_TRY(rc);
-    }
+    CZK_TRY(shm_rendezvous(n, name, table_bytes, &p));
     hipIpcMemHandle_t* handles = (hipIpcMemHandle_t*)p;
     auto fail = [&](const std::string& msg) {
         n->hdr->abort.store(1, std::memory_order_release);
@@ -311,20 +265,10 @@ int shm_data(czk_net* n) {   // the staging slots, created at the first exchange
     if (n->transport == CZK_NET_IPC) return ipc_data(n);
     if (n->slots) return CZK_OK;
     const std::string name = n->shm_name + ".d";
-    if (n->rank == 0) n->hdr->slot_bytes.store(n->slot_bytes, std::memory_order_release);
+    const auto slots_bytes = [](const czk_net* c) { return (size_t)c->world * 2 * c->slot_bytes; };
     void* p = nullptr;
-    int rc = CZK_OK;
-    if (n->rank == 0) rc = shm_map(n, name, (size_t)n->world * 2 * n->slot_bytes, true, &p);
-    if (rc != CZK_OK) n->hdr->abort.store(1, std::memory_order_release);
-    CZK_TRY(rc);
-    CZK_TRY(shm_barrier(n));   // rank 0 has created the segment and published its slot size
-    if (n->rank != 0) {
-        n->slot_bytes = (size_t)n->hdr->slot_bytes.load(std::memory_order_acquire);
-        rc = shm_map(n, name, (size_t)n->world * 2 * n->slot_bytes, false, &p);
-        if (rc != CZK_OK) n->hdr->abort.store(1, std::memory_order_release);
-        CZK_TRY(rc);
-    }
-    n->data_bytes = (size_t)n->world * 2 * n->slot_bytes;
+    CZK_TRY(shm_rendezvous(n, name, slots_bytes, &p));
+    n->data_bytes = slots_bytes(n);
     CZK_TRY(shm_barrier(n));   // everybody has it mapped
     if (n->rank == 0) shm_unlink(name.c_str());
     if (n->ctx) {              // pinned: the DMA engines read / write the segment directly
@@ -386,8 +330,6 @@ int shm_step_barrier(czk_net* n, bool wrote) {
     }
     return shm_barrier(n);
 }
-
-enum class Op { Broadcast, ToKing, FromKing, AllToAll };
 
 // One exchange in chunk steps of slot_bytes.  Step k uses the slots of parity k: a slot written in step k is read in step k and
 // next written in step k + 2, which lies behind barrier k + 1 -- and a rank arrives there only after its reads of step k completed.
@@ -499,8 +441,9 @@ void op_sizes(const czk_net* n, Op op, size_t bytes, size_t* send_b, size_t* rec
         case Op::AllToAll: *send_b = *recv_b = bytes * n->world; break;
     }
 }
+}  // namespace
 
-int exchange(czk_net* n, Op op, const void* send, size_t bytes, void* recv, int mem) {
+int czk::exchange(czk_net* n, Op op, const void* send, size_t bytes, void* recv, int mem) {
     if (!n) return CZK_ERR_ARG;
     if (!valid_mem(mem)) return net_err(n, CZK_ERR_ARG, "czk_net: mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
     size_t sb, rb;
@@ -526,7 +469,7 @@ int exchange(czk_net* n, Op op, const void* send, size_t bytes, void* recv, int 
     return CZK_OK;
 }
 
-void count_stats(czk_net* n, Op op, size_t m) {   // mpc-net/src/multi.rs:148-150, :179-193, :214-220
+void czk::count_stats(czk_net* n, Op op, size_t m) {   // mpc-net/src/multi.rs:148-150, :179-193, :214-220
     const uint64_t others = (uint64_t)(n->world - 1);
     switch (op) {
         case Op::Broadcast:
@@ -547,15 +490,8 @@ void count_stats(czk_net* n, Op op, size_t m) {   // mpc-net/src/multi.rs:148-15
             break;
     }
 }
-}  // namespace
 
 // ---- C ABI: communicator ---------------------------------------------------------------------------------------------------------------
-extern "C" void czk_sha256(const void* data, size_t len, uint8_t* out32) {
-    Sha256 s;
-    s.update(data, len);
-    s.finish(out32);
-}
-
 extern "C" int czk_net_unique_id(int transport, uint8_t* out, size_t cap, size_t* len) {
     if (!out || !len) return CZK_ERR_ARG;
     if (transport == CZK_NET_RCCL) {
@@ -693,26 +629,15 @@ extern "C" void czk_net_stats_reset(czk_net* n) {
     if (n) memset(n->stats, 0, sizeof n->stats);
 }
 
-extern "C" int czk_net_broadcast(czk_net* n, const void* send, size_t bytes, void* recv, int mem) {
-    CZK_TRY(exchange(n, Op::Broadcast, send, bytes, recv, mem));
-    count_stats(n, Op::Broadcast, bytes);
+static int counted_exchange(czk_net* n, Op op, const void* send, size_t bytes, void* recv, int mem) {   // a failed exchange counts nothing
+    CZK_TRY(exchange(n, op, send, bytes, recv, mem));
+    count_stats(n, op, bytes);
     return CZK_OK;
 }
-extern "C" int czk_net_send_to_king(czk_net* n, const void* send, size_t bytes, void* recv, int mem) {
-    CZK_TRY(exchange(n, Op::ToKing, send, bytes, recv, mem));
-    count_stats(n, Op::ToKing, bytes);
-    return CZK_OK;
-}
-extern "C" int czk_net_recv_from_king(czk_net* n, const void* send, size_t bytes, void* recv, int mem) {
-    CZK_TRY(exchange(n, Op::FromKing, send, bytes, recv, mem));
-    count_stats(n, Op::FromKing, bytes);
-    return CZK_OK;
-}
-extern "C" int czk_net_alltoall(czk_net* n, const void* send, size_t bytes, void* recv, int mem) {
-    CZK_TRY(exchange(n, Op::AllToAll, send, bytes, recv, mem));
-    count_stats(n, Op::AllToAll, bytes);
-    return CZK_OK;
-}
+extern "C" int czk_net_broadcast(czk_net* n, const void* send, size_t bytes, void* recv, int mem) { return counted_exchange(n, Op::Broadcast, send, bytes, recv, mem); }
+extern "C" int czk_net_send_to_king(czk_net* n, const void* send, size_t bytes, void* recv, int mem) { return counted_exchange(n, Op::ToKing, send, bytes, recv, mem); }
+extern "C" int czk_net_recv_from_king(czk_net* n, const void* send, size_t bytes, void* recv, int mem) { return counted_exchange(n, Op::FromKing, send, bytes, recv, mem); }
+extern "C" int czk_net_alltoall(czk_net* n, const void* send, size_t bytes, void* recv, int mem) { return counted_exchange(n, Op::AllToAll, send, bytes, recv, mem); }
 extern "C" int czk_net_barrier(czk_net* n) {
     if (!n) return CZK_ERR_ARG;
     if (n->shm_like()) {
@@ -726,515 +651,4 @@ extern "C" int czk_net_barrier(czk_net* n) {
     uint8_t one = 1;
     std::vector<uint8_t> all(n->world);
     return exchange(n, Op::Broadcast, &one, 1, all.data(), CZK_MEM_HOST);
-}
-
-// ---- wire format -----------------------------------------------------------------------------------------------------------------------
-extern "C" int czk_fr_vec_serialize(czk_ctx* ctx, const uint64_t* a, size_t n, int mem, uint8_t* out) {
-    if (!ctx) return CZK_ERR_ARG;
-    if (!out || (n && !a) || !valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "czk_fr_vec_serialize: null / bad argument");
-    const uint64_t len = n;
-    memcpy(out, &len, 8);   // u64 little-endian length (serialize/src/lib.rs:222-223); the hosts this library runs on are little-endian
-    if (!n) return CZK_OK;
-    if (mem == CZK_MEM_HOST) {
-        std::vector<uint64_t> rep(4 * n);
-        CZK_TRY(czk_fr_into_repr(ctx, a, rep.data(), n, CZK_MEM_HOST));
-        memcpy(out + 8, rep.data(), 32 * n);
-        return CZK_OK;
-    }
-    CZK_HIP(ctx, hipSetDevice(ctx->device));
-    DeviceBuf b;
-    CZK_TRY(stage_take(ctx, 32 * n, &b));
-    int rc = czk_fr_into_repr(ctx, a, (uint64_t*)b.p, n, CZK_MEM_DEVICE);
-    if (rc == CZK_OK) rc = download_pageable(ctx, out + 8, b.p, 32 * n);   // blocking
-    stage_give(ctx, b);
-    return rc;
-}
-
-extern "C" int czk_fr_vec_deserialize(czk_ctx* ctx, const uint8_t* bytes, size_t len, uint64_t* out, size_t cap, int mem, size_t* n_out) {
-    if (!ctx) return CZK_ERR_ARG;
-    if (!bytes || !n_out || len < 8 || !valid_mem(mem)) return set_err(ctx, CZK_ERR_ARG, "czk_fr_vec_deserialize: null / short input");
-    uint64_t n64;
-    memcpy(&n64, bytes, 8);
-    if (n64 > (len - 8) / 32 || 8 + 32 * (size_t)n64 != len) return set_err(ctx, CZK_ERR_ARG, "Vec<Fr> wire format: length prefix does not match the payload");
-    const size_t n = (size_t)n64;
-    *n_out = n;
-    if (n > cap || (n && !out)) return set_err(ctx, CZK_ERR_ARG, "czk_fr_vec_deserialize: more elements than the output holds");
-    if (!n) return CZK_OK;
-    std::vector<uint64_t> rep(4 * n);
-    memcpy(rep.data(), bytes + 8, 32 * n);
-    // Fp::deserialize -> from_repr fails on a non-canonical value (fields/macros.rs:443-454: `if r.is_valid()`)
-    static const uint64_t R_MOD[4] = {0x0a11800000000001ull, 0x59aa76fed0000001ull, 0x60b44d1e5c37b001ull, 0x12ab655e9a2ca556ull};
-    for (size_t i = 0; i < n; i++) {
-        bool lt = false;
-        for (int j = 3; j >= 0; j--) {
-            if (rep[4 * i + j] != R_MOD[j]) {
-                lt = rep[4 * i + j] < R_MOD[j];
-                break;
-            }
-        }
-        if (!lt) return set_err(ctx, CZK_ERR_ARG, "Vec<Fr> wire format: element not below the modulus");
-    }
-    if (mem == CZK_MEM_HOST) return czk_fr_from_repr(ctx, rep.data(), out, n, CZK_MEM_HOST);
-    CZK_HIP(ctx, hipSetDevice(ctx->device));
-    CZK_TRY(upload_pageable(ctx, out, rep.data(), 32 * n));   // returns once `rep` has been read
-    return czk_fr_from_repr(ctx, out, out, n, CZK_MEM_DEVICE);
-}
-
-// ---- atomic_broadcast and the batch opens ----------------------------------------------------------------------------------------------
-extern "C" int czk_net_atomic_broadcast(czk_net* n, const uint64_t* x, size_t cnt, uint64_t* recv, const uint8_t* rand32, int mem) {
-    if (!n) return CZK_ERR_ARG;
-    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "czk_net_atomic_broadcast needs a communicator created with a context");
-    if (cnt && (!x || !recv)) return net_err(n, CZK_ERR_ARG, "czk_net_atomic_broadcast: null buffer");
-    const int W = n->world;
-    const size_t ser = 8 + 32 * cnt;
-    std::vector<uint8_t> wire(ser + 32), commit(32), all_commits(32 * (size_t)W), all_rnd(32 * (size_t)W);
-    NET_CTX(n, czk_fr_vec_serialize(n->ctx, x, cnt, mem, wire.data()));
-    if (rand32) memcpy(&wire[ser], rand32, 32);
-    else if (getrandom(&wire[ser], 32, 0) != 32) return net_err(n, CZK_ERR_NET, "getrandom failed");
-    czk_sha256(wire.data(), wire.size(), commit.data());                                          // commitment = H(data || randomness)
-    CZK_TRY(exchange(n, Op::Broadcast, commit.data(), 32, all_commits.data(), CZK_MEM_HOST));   // exchange commitments
-    CZK_TRY(exchange(n, Op::Broadcast, x, 32 * cnt, recv, mem));                                 // exchange (data || randomness)
-    CZK_TRY(exchange(n, Op::Broadcast, &wire[ser], 32, all_rnd.data(), CZK_MEM_HOST));
-    count_stats(n, Op::Broadcast, 32);              // the reference's two broadcasts: 32 bytes, then ser + 32 bytes (channel.rs:58-61)
-    count_stats(n, Op::Broadcast, ser + 32);
-    for (int p = 0; p < W; p++) {
-        if (p == n->rank) continue;
-        NET_CTX(n, czk_fr_vec_serialize(n->ctx, recv + 4 * cnt * (size_t)p, cnt, mem, wire.data()));
-        memcpy(&wire[ser], &all_rnd[32 * (size_t)p], 32);
-        uint8_t h[32];
-        czk_sha256(wire.data(), wire.size(), h);
-        if (memcmp(h, &all_commits[32 * (size_t)p], 32) != 0)
-            return net_err(n, CZK_ERR_CHECK, "atomic_broadcast: party " + std::to_string(p) + "'s data does not match its commitment");
-    }
-    return CZK_OK;
-}
-
-// The same round with the tree commitment of commit_tree.hip: the same three exchanges with the same byte counts (a rank that made the SHA-256 call instead
-// meets this one in every exchange, and both fail the check), the same stats; the W gathered vectors are hashed in one pass on the device.
-extern "C" int czk_net_atomic_broadcast_tree(czk_net* n, const uint64_t* x, size_t cnt, uint64_t* recv, const uint8_t* rand32, int mem) {
-    if (!n) return CZK_ERR_ARG;
-    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "czk_net_atomic_broadcast_tree needs a communicator created with a context");
-    if (!valid_mem(mem)) return net_err(n, CZK_ERR_ARG, "czk_net: mem must be CZK_MEM_HOST or CZK_MEM_DEVICE");
-    if (cnt && (!x || !recv)) return net_err(n, CZK_ERR_ARG, "czk_net_atomic_broadcast_tree: null buffer");
-    const size_t W = (size_t)n->world;
-    std::vector<uint8_t> rnd(32), commit(32), all_commits(32 * W), all_rnd(32 * W), check(32 * W);
-    if (rand32) memcpy(rnd.data(), rand32, 32);
-    else if (getrandom(rnd.data(), 32, 0) != 32) return net_err(n, CZK_ERR_NET, "getrandom failed");
-    NET_CTX(n, czk_fr_vec_commit(n->ctx, x, 1, cnt, cnt, rnd.data(), commit.data(), mem));
-    CZK_TRY(exchange(n, Op::Broadcast, commit.data(), 32, all_commits.data(), CZK_MEM_HOST));   // exchange commitments
-    CZK_TRY(exchange(n, Op::Broadcast, x, 32 * cnt, recv, mem));                                 // exchange (data || randomness)
-    CZK_TRY(exchange(n, Op::Broadcast, rnd.data(), 32, all_rnd.data(), CZK_MEM_HOST));
-    count_stats(n, Op::Broadcast, 32);              // counted as the reference's two broadcasts (channel.rs:58-61), as czk_net_atomic_broadcast does
-    count_stats(n, Op::Broadcast, 8 + 32 * cnt + 32);
-    NET_CTX(n, czk_fr_vec_commit(n->ctx, recv, W, cnt, cnt, all_rnd.data(), check.data(), mem));   // (waits for the gathered vectors: stream order)
-    for (size_t p = 0; p < W; p++)
-        if ((int)p != n->rank && memcmp(&check[32 * p], &all_commits[32 * p], 32) != 0)
-            return net_err(n, CZK_ERR_CHECK, "atomic_broadcast: party " + std::to_string(p) + "'s data does not match its commitment");
-    return CZK_OK;
-}
-
-namespace {
-int open_args(czk_net* n, const void* a, const void* b, size_t cnt) {
-    if (!n) return CZK_ERR_ARG;
-    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "batch opens need a communicator created with a context");
-    if (cnt && (!a || !b)) return net_err(n, CZK_ERR_ARG, "batch open: null buffer");
-    NET_HIP(n, hipSetDevice(n->ctx->device));
-    return CZK_OK;
-}
-}  // namespace
-
-extern "C" int czk_spdz_batch_open(czk_net* n, const uint64_t* sh, const uint64_t* mac, const uint64_t* mac_share, size_t cnt, uint64_t* out_value,
-                                   int flags, uint64_t* out_bad) {
-    CZK_TRY(open_args(n, sh, out_value, cnt));
-    if (!out_bad || !mac_share || (cnt && !mac)) return net_err(n, CZK_ERR_ARG, "czk_spdz_batch_open: null argument");
-    *out_bad = 0;
-    if (!cnt) return CZK_OK;
-    const size_t W = (size_t)n->world;
-    CZK_TRY(net_buf(n, n->gather, W * cnt * 32));
-    CZK_TRY(net_buf(n, n->dx, cnt * 32));
-    uint64_t* g = (uint64_t*)n->gather.p;
-    uint64_t* dx = (uint64_t*)n->dx.p;
-    CZK_TRY(czk_net_broadcast(n, sh, cnt * 32, g, CZK_MEM_DEVICE));                       // let all_vals = Net::broadcast(&s_vals)
-    NET_CTX(n, czk_fr_lanes_sum(n->ctx, g, W, cnt, out_value, nullptr));                  // vals[i] = sum over the parties
-    NET_CTX(n, czk_fr_spdz_dx(n->ctx, out_value, mac, mac_share, dx, cnt));               // dx_t = mac_share * val - mac
-    if (flags & CZK_OPEN_COMMIT_TREE) CZK_TRY(czk_net_atomic_broadcast_tree(n, dx, cnt, g, nullptr, CZK_MEM_DEVICE));
-    else if (flags & CZK_OPEN_COMMIT) CZK_TRY(czk_net_atomic_broadcast(n, dx, cnt, g, nullptr, CZK_MEM_DEVICE));   // Net::atomic_broadcast(&dx_ts)
-    else CZK_TRY(czk_net_broadcast(n, dx, cnt * 32, g, CZK_MEM_DEVICE));
-    NET_CTX(n, czk_fr_lanes_sum(n->ctx, g, W, cnt, nullptr, out_bad));                    // assert!(sum.is_zero()) -- the caller's, on *out_bad
-    return CZK_OK;
-}
-
-extern "C" int czk_add_batch_open(czk_net* n, const uint64_t* val, size_t cnt, uint64_t* out_value) {
-    CZK_TRY(open_args(n, val, out_value, cnt));
-    if (!cnt) return CZK_OK;
-    const size_t W = (size_t)n->world;
-    CZK_TRY(net_buf(n, n->gather, W * cnt * 32));
-    CZK_TRY(czk_net_broadcast(n, val, cnt * 32, n->gather.p, CZK_MEM_DEVICE));
-    NET_CTX(n, czk_fr_lanes_sum(n->ctx, (const uint64_t*)n->gather.p, W, cnt, out_value, nullptr));
-    return CZK_OK;
-}
-
-namespace {
-// GszFieldShare::batch_open's exchange and launch, enqueued: `bad` non-null adds the violations to that device counter (no read-back); null makes the
-// blocking czk_fr_gsz_open count into *out_bad
-int gsz_open_trip(czk_net* n, const uint64_t* val, size_t cnt, const uint32_t* degrees, unsigned degree, uint64_t* out_value, unsigned long long* bad, uint64_t* out_bad) {
-    const size_t W = (size_t)n->world;
-    CZK_TRY(net_buf(n, n->gather, W * cnt * 32));
-    CZK_TRY(czk_net_broadcast(n, val, cnt * 32, n->gather.p, CZK_MEM_DEVICE));
-    if (bad) NET_CTX(n, gsz_open_enqueue(n->ctx, (const u64*)n->gather.p, W, cnt, degrees, degree, (u64*)out_value, bad));
-    else NET_CTX(n, czk_fr_gsz_open(n->ctx, (const uint64_t*)n->gather.p, W, cnt, degrees, degree, out_value, out_bad));
-    return CZK_OK;
-}
-// gsz20::batch_king_compute's two exchanges around the king's open, the same way
-int gsz_king_trip(czk_net* n, const uint64_t* val, size_t cnt, const uint32_t* degrees, unsigned degree, uint64_t* out, unsigned long long* bad, uint64_t* out_bad) {
-    const size_t W = (size_t)n->world;
-    const bool king = n->rank == 0;
-    // the king's scratch: world gathered lanes, then world identical answers (`vec![output; n]`, gsz20/mod.rs:508-512)
-    if (king) CZK_TRY(net_buf(n, n->gather, 2 * W * cnt * 32));
-    uint64_t* g = (uint64_t*)n->gather.p;
-    CZK_TRY(czk_net_send_to_king(n, val, cnt * 32, king ? g : nullptr, CZK_MEM_DEVICE));
-    uint64_t* ans = king ? g + 4 * W * cnt : nullptr;
-    if (king) {
-        // open_degree_vec per element, f = identity
-        if (bad) NET_CTX(n, gsz_open_enqueue(n->ctx, (const u64*)g, W, cnt, degrees, degree, (u64*)ans, bad));
-        else NET_CTX(n, czk_fr_gsz_open(n->ctx, g, W, cnt, degrees, degree, ans, out_bad));
-        for (size_t p = 1; p < W; p++)
-            NET_HIP(n, hipMemcpyAsync(ans + 4 * cnt * p, ans, cnt * 32, hipMemcpyDeviceToDevice, n->ctx->stream));
-    }
-    return czk_net_recv_from_king(n, ans, cnt * 32, out, CZK_MEM_DEVICE);
-}
-}  // namespace
-
-extern "C" int czk_gsz_batch_open(czk_net* n, const uint64_t* val, size_t cnt, const uint32_t* degrees, unsigned degree, uint64_t* out_value,
-                                  uint64_t* out_bad) {
-    CZK_TRY(open_args(n, val, out_value, cnt));
-    if (!out_bad) return net_err(n, CZK_ERR_ARG, "czk_gsz_batch_open: null out_bad");
-    *out_bad = 0;
-    if (!cnt) return CZK_OK;
-    return gsz_open_trip(n, val, cnt, degrees, degree, out_value, nullptr, out_bad);
-}
-
-extern "C" int czk_fr_send_to_king(czk_net* n, const uint64_t* x, size_t cnt, uint64_t* gathered) {
-    if (!n) return CZK_ERR_ARG;
-    return czk_net_send_to_king(n, x, cnt * 32, gathered, CZK_MEM_DEVICE);
-}
-extern "C" int czk_fr_recv_from_king(czk_net* n, const uint64_t* parts, size_t cnt, uint64_t* out) {
-    if (!n) return CZK_ERR_ARG;
-    return czk_net_recv_from_king(n, parts, cnt * 32, out, CZK_MEM_DEVICE);
-}
-
-extern "C" int czk_gsz_batch_king_compute(czk_net* n, const uint64_t* val, size_t cnt, const uint32_t* degrees, unsigned degree, uint64_t* out,
-                                          uint64_t* out_bad) {
-    CZK_TRY(open_args(n, val, out, cnt));
-    if (!out_bad) return net_err(n, CZK_ERR_ARG, "czk_gsz_batch_king_compute: null out_bad");
-    *out_bad = 0;
-    if (!cnt) return CZK_OK;
-    return gsz_king_trip(n, val, cnt, degrees, degree, out, nullptr, out_bad);
-}
-
-// ---- FieldShare::batch_mul / batch_inv / partial_products for one party per communicator (share/field.rs:97-182; kernels in share_mul.hip) -----------------
-// Every round is the reference's, in its order, except that the two independent opens of a batch_mul go out as ONE open of 2 cnt elements.
-namespace {
-struct NetShare {
-    czk_net* n;
-    size_t lpp;
-    const uint64_t* mac_share;   // host; SPDZ only
-    Fr ms;
-    int flags;
-    uint64_t bad = 0;
-};
-int net_share_args(czk_net* n, const char* what, size_t lpp, const uint64_t* mac_share, bool null_vec, size_t cnt, int flags, uint64_t* out_bad, uint64_t* out_zero,
-                   NetShare* s, bool* work) {
-    *work = false;
-    if (!n) return CZK_ERR_ARG;
-    if (!n->ctx) return net_err(n, CZK_ERR_ARG, std::string(what) + " needs a communicator created with a context");
-    if (!out_bad || !out_zero) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null count output");
-    *out_bad = *out_zero = 0;
-    if (lpp != 1 && lpp != 2) return net_err(n, CZK_ERR_ARG, std::string(what) + ": lpp is 1 (additive) or 2 (SPDZ)");
-    if (!cnt) return CZK_OK;
-    if (null_vec || (lpp == 2 && !mac_share)) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null argument");
-    if (cnt > ((size_t)1 << 54)) return net_err(n, CZK_ERR_SIZE, std::string(what) + ": the lane arrays' byte count overflows");
-    NET_HIP(n, hipSetDevice(n->ctx->device));
-    s->n = n, s->lpp = lpp, s->mac_share = mac_share, s->flags = flags;
-    s->ms = lpp == 2 ? host_fr(mac_share) : Fr::zero();
-    *work = true;
-    return CZK_OK;
-}
-// the scheme's batch_open of this party's lanes (cnt apart); failed MAC checks add up in s.bad
-int net_share_open(NetShare& s, const u64* lanes, size_t cnt, u64* out_value) {
-    if (s.lpp == 1) return czk_add_batch_open(s.n, lanes, cnt, out_value);
-    uint64_t b = 0;
-    CZK_TRY(czk_spdz_batch_open(s.n, lanes, lanes + 4 * cnt, s.mac_share, cnt, out_value, s.flags, &b));
-    s.bad += b;
-    return CZK_OK;
-}
-size_t net_share_mul_ws(size_t lpp, size_t cnt) { return (lpp + 1) * 2 * cnt * 32; }
-// ws: lpp x 2 cnt masked factors, then the 2 cnt opened values
-int net_share_mul(NetShare& s, ShareVec x, ShareVec y, const u64* tx, const u64* ty, const u64* tz, size_t T, size_t first, u64* ws, u64* out, size_t cnt) {
-    czk_net* n = s.n;
-    u64* opened = ws + 4 * s.lpp * 2 * cnt;
-    const ShareVec vx{tx + 4 * first, T, 1}, vy{ty + 4 * first, T, 1}, vz{tz + 4 * first, T, 1};
-    NET_CTX(n, share_mask_launch(n->ctx, (unsigned)s.lpp, x, y, vx, vy, ws, cnt));
-    CZK_TRY(net_share_open(s, ws, 2 * cnt, opened));
-    NET_CTX(n, share_combine_launch(n->ctx, (unsigned)s.lpp, n->rank == 0, s.ms, opened, vx, vy, vz, out, cnt, cnt));
-    return CZK_OK;
-}
-}  // namespace
-
-extern "C" int czk_net_share_batch_mul(czk_net* n, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* y, const uint64_t* tx,
-                                       const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t cnt, int flags, uint64_t* out_bad, uint64_t* out_zero) {
-    NetShare s;
-    bool work;
-    CZK_TRY(net_share_args(n, "czk_net_share_batch_mul", lpp, mac_share, !x || !y || !tx || !ty || !tz || !out, cnt, flags, out_bad, out_zero, &s, &work));
-    if (!work) return CZK_OK;
-    StageHold ws(n->ctx);
-    NET_CTX(n, ws.take(net_share_mul_ws(lpp, cnt)));
-    CZK_TRY(net_share_mul(s, ShareVec{x, cnt, 1}, ShareVec{y, cnt, 1}, tx, ty, tz, cnt, 0, (u64*)ws.b.p, out, cnt));
-    NET_HIP(n, hipStreamSynchronize(n->ctx->stream));   // like the opens: the call's outputs are complete when it returns
-    *out_bad = s.bad;
-    return CZK_OK;
-}
-
-extern "C" int czk_net_share_batch_inv(czk_net* n, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
-                                       const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t cnt, int flags, uint64_t* out_bad,
-                                       uint64_t* out_zero) {
-    NetShare s;
-    bool work;
-    CZK_TRY(net_share_args(n, "czk_net_share_batch_inv", lpp, mac_share, !x || !pb || !pc || !tx || !ty || !tz || !out, cnt, flags, out_bad, out_zero, &s, &work));
-    if (!work) return CZK_OK;
-    StageHold ws(n->ctx);
-    NET_CTX(n, ws.take(net_share_mul_ws(lpp, cnt) + (lpp + 2) * cnt * 32));
-    u64 *mulws = (u64*)ws.b.p, *prod = mulws + net_share_mul_ws(lpp, cnt) / 8, *v = prod + 4 * lpp * cnt, *vinv = v + 4 * cnt;
-    CZK_TRY(net_share_mul(s, ShareVec{x, cnt, 1}, ShareVec{pb, cnt, 1}, tx, ty, tz, cnt, 0, mulws, prod, cnt));
-    CZK_TRY(net_share_open(s, prod, cnt, v));
-    NET_CTX(n, czk_fr_batch_inverse(n->ctx, v, cnt, nullptr, vinv, CZK_MEM_DEVICE));
-    NET_CTX(n, share_counters(n->ctx));
-    NET_CTX(n, share_scale_launch(n->ctx, (unsigned)lpp, ShareVec{pc, cnt, 1}, vinv, nullptr, out, cnt, cnt));
-    NET_CTX(n, share_counters_read(n->ctx, nullptr, out_zero));
-    *out_bad = s.bad;
-    return CZK_OK;
-}
-
-extern "C" int czk_net_share_partial_products(czk_net* n, size_t lpp, const uint64_t* mac_share, const uint64_t* x, const uint64_t* pb, const uint64_t* pc,
-                                              const uint64_t* tx, const uint64_t* ty, const uint64_t* tz, uint64_t* out, size_t cnt, int flags, uint64_t* out_bad,
-                                              uint64_t* out_zero) {
-    NetShare s;
-    bool work;
-    CZK_TRY(net_share_args(n, "czk_net_share_partial_products", lpp, mac_share, !x || !pb || !pc || !tx || !ty || !tz || !out, cnt, flags, out_bad, out_zero, &s,
-                           &work));
-    if (!work) return CZK_OK;
-    const size_t T = 4 * cnt, P = 2 * cnt + 1;
-    StageHold ws(n->ctx);
-    NET_CTX(n, ws.take(net_share_mul_ws(lpp, cnt) + (2 * lpp + 4) * cnt * 32));
-    u64 *mulws = (u64*)ws.b.p, *la = mulws + net_share_mul_ws(lpp, cnt) / 8, *lb = la + 4 * lpp * cnt, *mxm = lb + 4 * lpp * cnt, *run = mxm + 4 * cnt, *mms = run + 4 * cnt,
-        *inv = mms + 4 * cnt;
-    const ShareVec m_inv1{pc + 4, P, 1};                                                                     // m_inv[1..]
-    CZK_TRY(net_share_mul(s, ShareVec{pb, P, 1}, ShareVec{x, cnt, 1}, tx, ty, tz, T, 0, mulws, la, cnt));   // mx = m[..n] x
-    CZK_TRY(net_share_mul(s, ShareVec{la, cnt, 1}, m_inv1, tx, ty, tz, T, cnt, mulws, lb, cnt));            // mxm = mx m_inv[1..]
-    CZK_TRY(net_share_open(s, lb, cnt, mxm));
-    NET_CTX(n, czk_fr_prefix_product(n->ctx, mxm, cnt, run, CZK_MEM_DEVICE));                               // the local loop :169-172
-    CZK_TRY(net_share_mul(s, ShareVec{pb, P, 0}, m_inv1, tx, ty, tz, T, 2 * cnt, mulws, la, cnt));          // mms = m_0 m_inv[1..]
-    CZK_TRY(net_share_mul(s, ShareVec{la, cnt, 1}, ShareVec{pb + 4 * (cnt + 1), P, 1}, tx, ty, tz, T, 3 * cnt, mulws, lb, cnt));   // batch_inv(mms)
-    CZK_TRY(net_share_open(s, lb, cnt, mms));
-    NET_CTX(n, czk_fr_batch_inverse(n->ctx, mms, cnt, nullptr, inv, CZK_MEM_DEVICE));
-    NET_CTX(n, share_counters(n->ctx));
-    NET_CTX(n, share_scale_launch(n->ctx, (unsigned)lpp, ShareVec{pc + 4 * (cnt + 1), P, 1}, inv, run, out, cnt, cnt));
-    NET_CTX(n, share_counters_read(n->ctx, nullptr, out_zero));
-    *out_bad = s.bad;
-    return CZK_OK;
-}
-
-// ---- gsz20's batch_mult / batch_inv / partial_products and its product check for one party per communicator (share/gsz20/mod.rs:559-594, :325-366,
-// :596-808; kernels in gsz_mul.hip) ------------------------------------------------------------------------------------------------------------------------
-// The party is the communicator's rank and holds ONE lane of every vector.  Every exchange is the reference's, in its dependency order; the king's open
-// and the plain opens count their degree violations in ctx->share_cnt, read back once at the end of the call.
-namespace {
-struct NetGsz {
-    czk_net* n;
-    unsigned degree;
-    const u64 *dr, *dr2, *rands;   // this party's lanes of the material
-    unsigned long long* cnt;       // ctx->share_cnt
-};
-int net_gsz_args(czk_net* n, const char* what, unsigned degree, bool null_vec, size_t cnt, uint64_t* out_a, uint64_t* out_b, NetGsz* s, bool* work) {
-    *work = false;
-    if (!n) return CZK_ERR_ARG;
-    if (!n->ctx) return net_err(n, CZK_ERR_ARG, std::string(what) + " needs a communicator created with a context");
-    if (!out_a || !out_b) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null result output");
-    *out_a = *out_b = 0;
-    const size_t W = (size_t)n->world;
-    if (W > 96) return net_err(n, CZK_ERR_SIZE, std::string(what) + ": more than 96 parties");
-    u64 dom[12];
-    NET_CTX(n, czk_share_domain_constants(n->ctx, W, dom));   // CZK_ERR_SIZE: no share domain of that size
-    if (!cnt) return CZK_OK;
-    if (null_vec) return net_err(n, CZK_ERR_ARG, std::string(what) + ": null argument");
-    if (cnt > ((size_t)1 << 52) / W) return net_err(n, CZK_ERR_SIZE, std::string(what) + ": the lane arrays' byte count overflows");
-    NET_HIP(n, hipSetDevice(n->ctx->device));
-    NET_CTX(n, share_counters(n->ctx));
-    s->n = n, s->degree = degree < W ? degree : (unsigned)W, s->cnt = n->ctx->share_cnt;
-    *work = true;
-    return CZK_OK;
-}
-int net_gsz_king(NetGsz& s, const u64* val, size_t cnt, u64* out) { return gsz_king_trip(s.n, val, cnt, nullptr, 2 * s.degree, out, s.cnt, nullptr); }
-int net_gsz_open(NetGsz& s, const u64* val, size_t cnt, u64* out_value) { return gsz_open_trip(s.n, val, cnt, nullptr, s.degree, out_value, s.cnt, nullptr); }
-// one batch_mult with doubles [d_first, d_first + cnt): ws = 2 cnt elements; out = this party's share of x y
-int net_gsz_mul(NetGsz& s, ShareVec x, ShareVec y, size_t d_first, u64* ws, u64* out, size_t cnt) {
-    u64 *d = ws, *v = ws + 4 * cnt;
-    NET_CTX(s.n, gsz_net_mask_launch(s.n->ctx, x, y, s.dr2 + 4 * d_first, d, cnt));
-    CZK_TRY(net_gsz_king(s, d, cnt, v));
-    NET_CTX(s.n, gsz_net_unmask_launch(s.n->ctx, v, s.dr + 4 * d_first, out, cnt));
-    return CZK_OK;
-}
-// open(batch_mult(x, y)): the product's share goes from the workspace straight to the broadcast; opened: cnt values
-int net_gsz_mul_open(NetGsz& s, ShareVec x, ShareVec y, size_t d_first, u64* ws, u64* opened, size_t cnt) {
-    CZK_TRY(net_gsz_mul(s, x, y, d_first, ws, ws, cnt));   // (v - r lands on the masked values, which the king already has)
-    return net_gsz_open(s, ws, cnt, opened);
-}
-// batch_inv (:325-342) with rs = rands [r_first, ..), doubles [d_first, ..): ws = 4 cnt elements; out = rs / open(x rs) (times prefix, when given)
-int net_gsz_inv(NetGsz& s, ShareVec x, size_t d_first, size_t r_first, u64* ws, const u64* prefix, u64* out, size_t cnt) {
-    const ShareVec rs{s.rands + 4 * r_first, 0, 1};
-    u64 *v = ws + 4 * 2 * cnt, *vinv = v + 4 * cnt;
-    CZK_TRY(net_gsz_mul_open(s, x, rs, d_first, ws, v, cnt));
-    NET_CTX(s.n, czk_fr_batch_inverse(s.n->ctx, v, cnt, nullptr, vinv, CZK_MEM_DEVICE));
-    NET_CTX(s.n, share_scale_launch(s.n->ctx, 1, rs, vinv, prefix, out, cnt, cnt));
-    return CZK_OK;
-}
-}  // namespace
-
-extern "C" int czk_net_gsz_share_batch_mul(czk_net* n, unsigned degree, const uint64_t* x, const uint64_t* y, const uint64_t* doubles_r, const uint64_t* doubles_r2,
-                                           uint64_t* out, size_t cnt, uint64_t* out_bad, uint64_t* out_zero) {
-    NetGsz s;
-    bool work;
-    CZK_TRY(net_gsz_args(n, "czk_net_gsz_share_batch_mul", degree, !x || !y || !doubles_r || !doubles_r2 || !out, cnt, out_bad, out_zero, &s, &work));
-    if (!work) return CZK_OK;
-    s.dr = doubles_r, s.dr2 = doubles_r2, s.rands = nullptr;
-    StageHold ws(n->ctx);
-    NET_CTX(n, ws.take(2 * cnt * 32));
-    CZK_TRY(net_gsz_mul(s, ShareVec{x, 0, 1}, ShareVec{y, 0, 1}, 0, (u64*)ws.b.p, out, cnt));
-    NET_CTX(n, share_counters_read(n->ctx, out_bad, out_zero));
-    return CZK_OK;
-}
-
-extern "C" int czk_net_gsz_share_batch_inv(czk_net* n, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2, const uint64_t* rands,
-                                           uint64_t* out, size_t cnt, uint64_t* out_bad, uint64_t* out_zero) {
-    NetGsz s;
-    bool work;
-    CZK_TRY(net_gsz_args(n, "czk_net_gsz_share_batch_inv", degree, !x || !doubles_r || !doubles_r2 || !rands || !out, cnt, out_bad, out_zero, &s, &work));
-    if (!work) return CZK_OK;
-    s.dr = doubles_r, s.dr2 = doubles_r2, s.rands = rands;
-    StageHold ws(n->ctx);
-    NET_CTX(n, ws.take(4 * cnt * 32));
-    CZK_TRY(net_gsz_inv(s, ShareVec{x, 0, 1}, 0, 0, (u64*)ws.b.p, nullptr, out, cnt));
-    NET_CTX(n, share_counters_read(n->ctx, out_bad, out_zero));
-    return CZK_OK;
-}
-
-extern "C" int czk_net_gsz_share_partial_products(czk_net* n, unsigned degree, const uint64_t* x, const uint64_t* doubles_r, const uint64_t* doubles_r2,
-                                                  const uint64_t* rands, uint64_t* out, size_t cnt, uint64_t* out_bad, uint64_t* out_zero) {
-    NetGsz s;
-    bool work;
-    CZK_TRY(net_gsz_args(n, "czk_net_gsz_share_partial_products", degree, !x || !doubles_r || !doubles_r2 || !rands || !out, cnt, out_bad, out_zero, &s, &work));
-    if (!work) return CZK_OK;
-    s.dr = doubles_r, s.dr2 = doubles_r2, s.rands = rands;
-    const size_t c1 = cnt + 1;
-    StageHold ws(n->ctx);
-    NET_CTX(n, ws.take((4 * c1 + c1 + 3 * cnt) * 32));
-    u64 *mulws = (u64*)ws.b.p, *m_inv = mulws + 4 * 4 * c1, *lane = m_inv + 4 * c1, *mxm = lane + 4 * cnt, *run = mxm + 4 * cnt;
-    const ShareVec m{rands, 0, 1}, m0{rands, 0, 0}, m_inv1{m_inv + 4, 0, 1};                                            // m = rands [0, n]; m_inv[1..]
-    CZK_TRY(net_gsz_inv(s, m, 0, cnt + 1, mulws, nullptr, m_inv, c1));                                                   // m_inv = batch_inv(m)
-    CZK_TRY(net_gsz_mul(s, m, ShareVec{x, 0, 1}, cnt + 1, mulws, lane, cnt));                                            // mx = m[..n] x
-    CZK_TRY(net_gsz_mul_open(s, ShareVec{lane, 0, 1}, m_inv1, 2 * cnt + 1, mulws, mxm, cnt));                            // open(mx m_inv[1..])
-    NET_CTX(n, czk_fr_prefix_product(n->ctx, mxm, cnt, run, CZK_MEM_DEVICE));                                            // the local loop :353-356
-    CZK_TRY(net_gsz_mul(s, m0, m_inv1, 3 * cnt + 1, mulws, lane, cnt));                                                  // mms = m_0 m_inv[1..]
-    CZK_TRY(net_gsz_inv(s, ShareVec{lane, 0, 1}, 4 * cnt + 1, 2 * cnt + 2, mulws, run, out, cnt));                       // batch_inv(mms), scaled by the running product
-    NET_CTX(n, share_counters_read(n->ctx, out_bad, out_zero));
-    return CZK_OK;
-}
-
-extern "C" int czk_net_gsz_product_check(czk_net* n, unsigned degree, const uint64_t* xs, const uint64_t* ys, const uint64_t* zs, size_t cnt, const uint64_t* doubles_r,
-                                         const uint64_t* doubles_r2, const uint64_t* rands, uint64_t* out_ok, uint64_t* out_bad) {
-    NetGsz s;
-    bool work;
-    CZK_TRY(net_gsz_args(n, "czk_net_gsz_product_check", degree, !xs || !ys || !zs || !doubles_r || !doubles_r2 || !rands, cnt, out_ok, out_bad, &s, &work));
-    *out_ok = 1;   // no triples: nothing to refute
-    if (!work) return CZK_OK;
-    if (cnt >> 32) return net_err(n, CZK_ERR_SIZE, "czk_net_gsz_product_check: more than 2^32 - 1 triples");
-    czk_ctx* ctx = n->ctx;
-    unsigned R = 0;
-    while (((size_t)1 << R) < cnt) R++;
-    StageHold ws(ctx);
-    NET_CTX(n, ws.take(gsz_net_check_ws(ctx, cnt) * 32));
-    GszNetCheck c;
-    gsz_net_check_carve(ctx, c, (u64*)ws.b.p, cnt, doubles_r, doubles_r2, rands);
-    CZK_TRY(net_gsz_open(s, rands, 1, c.coin));                       // the hadamard coin (:601): the triples were committed before the call
-    NET_CTX(n, gsz_net_check_hadamard(ctx, c, xs, ys, zs));
-    for (unsigned round = 0; round < R; round++) {
-        NET_CTX(n, gsz_net_check_round_send(ctx, c));
-        CZK_TRY(net_gsz_king(s, c.wire, 2, c.king));                  // ip_l and ip3 in ONE round trip (both ip_compute calls precede the coin, :757, :690-692)
-        CZK_TRY(net_gsz_open(s, rands + 4 * c.r0, 1, c.opened));      // only now the round's coin
-        NET_CTX(n, gsz_net_check_round_recv(ctx, c));
-    }
-    NET_CTX(n, gsz_net_check_final(ctx, c, 0));
-    CZK_TRY(net_gsz_king(s, c.wire, 3, c.king));                      // mult(xr, yr), mult(x, xr), mult(y, yr)
-    NET_CTX(n, gsz_net_check_final(ctx, c, 1));
-    CZK_TRY(net_gsz_king(s, c.wire, 1, c.king));                      // mult(ip, ip_r) needs the first trip's answer
-    NET_CTX(n, gsz_net_check_final(ctx, c, 2));
-    CZK_TRY(net_gsz_open(s, c.blind, 3, c.opened));                   // the three blinded values in one broadcast
-    NET_CTX(n, gsz_net_check_final(ctx, c, 3));
-    uint64_t failed = 0;
-    NET_CTX(n, share_counters_read(ctx, out_bad, &failed));          // the one read-back of the check
-    *out_ok = failed ? 0 : 1;
-    return CZK_OK;
-}
-
-// ---- czk_net_gsz_dn_*: the GSZ material dealt and extracted with one party per communicator (kernels in gsz_dn.hip) --------------------------------------
-// The party deals under its OWN key alone; one all-to-all carries its shares out and the others' in; the extraction is local.  No rank sees another's key.
-extern "C" int czk_net_gsz_dn_generate(czk_net* n, int kind, unsigned degree, const uint8_t* key, const uint8_t* nonce, size_t deal, uint64_t* out_r, uint64_t* out_r2) {
-    if (!n) return CZK_ERR_ARG;
-    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_generate needs a communicator created with a context");
-    czk_ctx* ctx = n->ctx;
-    const size_t W = (size_t)n->world;
-    NET_CTX(n, gsz_dn_shape(ctx, "czk_net_gsz_dn_generate", kind, W, degree, deal));
-    if (!deal) return CZK_OK;
-    const bool doubles = kind == CZK_GSZ_DN_DOUBLES;
-    if (!key || !nonce || !out_r || (doubles && !out_r2)) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_generate: null argument");
-    NET_HIP(n, hipSetDevice(ctx->device));
-    const size_t per = (doubles ? 2 : 1) * deal;   // elements per peer
-    StageHold ws(ctx);
-    NET_CTX(n, ws.take((96 + 2 * W * per) * 32));
-    u64 *points = (u64*)ws.b.p, *send = points + 4 * 96, *recv = send + 4 * W * per;
-    NET_CTX(n, gsz_dn_points_launch(ctx, W, points));
-    NET_CTX(n, gsz_dn_deal_launch(ctx, kind, W, degree, key, nonce, deal, points, send));
-    CZK_TRY(czk_net_alltoall(n, send, per * 32, recv, CZK_MEM_DEVICE));
-    NET_CTX(n, gsz_dn_extract_launch(ctx, kind, W, degree, deal, points, recv, out_r, doubles ? out_r2 : nullptr));
-    return CZK_OK;
-}
-
-extern "C" int czk_net_gsz_dn_check(czk_net* n, int kind, unsigned degree, const uint64_t* r, const uint64_t* r2, size_t outputs, uint64_t* out_ok, uint64_t* out_bad) {
-    if (!n) return CZK_ERR_ARG;
-    if (!n->ctx) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check needs a communicator created with a context");
-    if (!out_ok || !out_bad) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check: null result output");
-    *out_ok = *out_bad = 0;
-    czk_ctx* ctx = n->ctx;
-    NET_CTX(n, gsz_dn_shape(ctx, "czk_net_gsz_dn_check", kind, (size_t)n->world, degree, 0));
-    const bool doubles = kind == CZK_GSZ_DN_DOUBLES;
-    if (outputs < 3) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check: fewer than 3 outputs (two are sacrificed)");
-    if (!r || (doubles && !r2)) return net_err(n, CZK_ERR_ARG, "czk_net_gsz_dn_check: null argument");
-    if (outputs >> 32) return net_err(n, CZK_ERR_SIZE, "czk_net_gsz_dn_check: more than 2^32 - 1 outputs");
-    NET_HIP(n, hipSetDevice(ctx->device));
-    const size_t cws = gsz_dn_combine_ws(ctx, 1, outputs);
-    StageHold ws(ctx);
-    NET_CTX(n, ws.take((cws + 5) * 32));
-    u64 *u = (u64*)ws.b.p + 4 * cws, *coin = u + 4 * 2, *opened = coin + 4;
-    NET_CTX(n, share_counters(ctx));
-    CZK_TRY(gsz_open_trip(n, r + 4 * (outputs - 2), 1, nullptr, degree, coin, ctx->share_cnt, nullptr));   // the coin: the first sacrificed output, opened
-    NET_CTX(n, gsz_dn_combine_launch(ctx, 1, r, doubles ? r2 : nullptr, outputs, outputs, coin, (u64*)ws.b.p, u));
-    CZK_TRY(gsz_open_trip(n, u, 1, nullptr, degree, opened, ctx->share_cnt, nullptr));
-    if (doubles) {
-        CZK_TRY(gsz_open_trip(n, u + 4, 1, nullptr, 2 * degree, opened + 4, ctx->share_cnt, nullptr));
-        NET_CTX(n, gsz_dn_verdict_launch(ctx, opened));
-    }
-    uint64_t differ = 0;
-    NET_CTX(n, share_counters_read(ctx, out_bad, &differ));   // the one read-back of the check
-    *out_ok = (differ || *out_bad) ? 0 : 1;
-    return CZK_OK;
 }

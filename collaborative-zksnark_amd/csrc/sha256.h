@@ -1,4 +1,4 @@
-// sha256.h -- SHA-256 (FIPS 180-4) on the host: the reference's CommitHash (mpc-algebra/src/channel.rs:92) behind czk_sha256 / czk_net_atomic_broadcast (net.hip),
+// sha256.h -- SHA-256 (FIPS 180-4) on the host: the reference's CommitHash (mpc-algebra/src/channel.rs:92) behind czk_sha256 / czk_net_atomic_broadcast (net_rounds.hip),
 // and the tag states and the model-side pieces of the tree commitment (commit_tree.hip).  Host code only.
 #pragma once
 #include <cstddef>

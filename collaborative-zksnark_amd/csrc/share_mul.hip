@@ -6,7 +6,7 @@
 //     once, the output lanes are written once (for up to SHARE_MUL_REG_LANES lanes the triple's x / y shares stay in registers between the open and
 //     the combine; beyond that they are read a second time by the thread that just read them).  Where the product only feeds an open
 //     (batch_inv's x b, partial_products' m x m_inv) the kernel opens it on the spot and writes the n opened values instead of the lanes.
-//   net form: one party per communicator (net.hip): k_share_mask writes both masked factors of the party's lanes into the contiguous 2n open
+//   net form: one party per communicator (net_rounds.hip): k_share_mask writes both masked factors of the party's lanes into the contiguous 2n open
 //     buffer -- the two opens of a batch_mul are independent and go out as ONE open -- and k_share_combine combines the lanes after it.
 //   k_share_scale: out_l = c_l * (k * prefix), the last step of batch_inv (prefix absent) and of partial_products (the running products of the
 //     opened values are never written per lane).

@@ -1,4 +1,4 @@
-"""czk_net_alltoall and czk_net_gsz_dn_generate / czk_net_gsz_dn_check (csrc/net.hip, kernels in csrc/gsz_dn.hip): the GSZ material dealt and extracted
+"""czk_net_alltoall and czk_net_gsz_dn_generate / czk_net_gsz_dn_check (csrc/net.hip, csrc/net_rounds.hip, kernels in csrc/gsz_dn.hip): the GSZ material dealt and extracted
 with ONE PARTY PER PROCESS, 3 and 4 processes sharing the GPU over CZK_NET_SHM.  The all-to-all delivers every byte through several chunk steps with a
 ragged tail; every rank's generated lane is its lane of the lanes form on the same keys; the check gives every rank the lanes form's verdict in the
 documented broadcasts, also when one dealt share is off by one; the generated material drives gsz20's product and product check; tails and write

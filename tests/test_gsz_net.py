@@ -1,4 +1,4 @@
-"""czk_net_gsz_share_batch_mul / _batch_inv / _partial_products and czk_net_gsz_product_check (csrc/net.hip, kernels in csrc/gsz_mul.hip): the GSZ
+"""czk_net_gsz_share_batch_mul / _batch_inv / _partial_products and czk_net_gsz_product_check (csrc/net_rounds.hip, kernels in csrc/gsz_mul.hip): the GSZ
 products and their product check with ONE PARTY PER PROCESS, 3 and 4 processes sharing the GPU over CZK_NET_SHM.  Every rank's output is its lane of
 the big-integer model (tests/gsz_mul_model.py), which the lanes form equals on the same case; the verdict is the same on every rank; the exchanges are
 the ones include/czk.h counts; a cheating party is seen by the king's bound at 4 parties and only by the check at 3; tails and write footprints on a

@@ -4,7 +4,7 @@ their edges, against tests/sat_model.py.
 On the device field.h's add / sub / double / reduce and every column of the Montgomery multiply are inline-assembly carry chains that the
 host never executes, so a check compiled for the host proves nothing about them.  czk_lab_arith_probe (ops from 200 up, lab library only)
 runs one function per item on raw limbs, in both forms build.py compiles field.h in: `name` with the multiply inlined (the hot kernels'
-form), `name@noinline` with -DCZK_NOINLINE_MUL (the form of pairing.hip, point_codec.hip, msm.hip, lanes.hip, net.hip; the only form the
+form), `name@noinline` with -DCZK_NOINLINE_MUL (the form of pairing.hip, point_codec.hip, msm.hip, lanes.hip, net.hip, net_rounds.hip; the only form the
 tower has).  Field and tower results are compared word for word with the model; curve results as group elements with oracle/pyref.py's
 affine law and, where a host entry point runs the same header (czk_jac_add, czk_jac_add_mixed, czk_jac_to_affine, czk_jac_scalar_mul by
 2), bit for bit with the portable host path.  Every family is fed whole; its size is the one tests/test_sat_arith_cpu.py established.
