@@ -297,6 +297,33 @@ class Context:
             out[name] = a[:, :out[k]]
         return out
 
+    def lab_msm_buckets(self, bases: "Bases", B: int, sorted_, offsets, counts, perm, dims_only: bool = False):
+        """czk_lab_msm_buckets (csrc/lab/msm_bucket_probe.hip, lab library only): the bucket accumulation, the over-full-bucket and fix-up
+        kernels and the bucket reduction of one MSM call on entry lists the caller wrote, over the tables of a registered key.  sorted_:
+        (lanes, total) u32 entry codes (w * nb + i) | sign << 31; offsets, counts, perm: (lanes, B) u32.  Returns the dimensions (c, W, nb,
+        family: 0 twisted Edwards / 1 u-form XYZZ / 2 saturated XYZZ, heavy_chunk, heavy_sub, exc_cap, heavy_cap) and, unless dims_only,
+        "buckets" (lanes, B, 18|36) Jacobian triples after the fix-up, the counters "exc_count", "dirty", "items", "heavy", "overflow", and
+        "result" (lanes, 18|36).  A list the kernels could not read safely raises CzkError.  Raises unless the context was opened with lab=True."""
+        if not self._lab:
+            raise RuntimeError("lab_msm_buckets needs Context(lab=True): libczk_hip.so does not export czk_lab_msm_buckets")
+        srt = np.ascontiguousarray(sorted_, dtype=np.uint32)
+        arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in (offsets, counts, perm)]
+        if srt.ndim != 2 or any(a.shape != (srt.shape[0], B) for a in arrs):
+            raise ValueError("sorted must have the shape (lanes, total); offsets, counts and perm (lanes, B)")
+        lanes, total = srt.shape
+        jw = 18 if bases.group == CZK_G1 else 36
+        dims = np.zeros(8, dtype=np.uint64)
+        buckets = np.zeros((lanes, B, jw), dtype=np.uint64)
+        counters = np.zeros(5, dtype=np.uint32)
+        result = np.zeros((lanes, jw), dtype=np.uint64)
+        outs = [None, None, None] if dims_only else [buckets, counters, result]
+        self._ck(self._L.czk_lab_msm_buckets(self._h, bases._h, C.c_size_t(lanes), C.c_size_t(B), C.c_size_t(total), _ptr(srt), *[_ptr(a) for a in arrs],
+                                             _ptr(dims), *[_ptr(o) for o in outs]))
+        out = dict(zip(("c", "W", "nb", "family", "heavy_chunk", "heavy_sub", "exc_cap", "heavy_cap"), (int(v) for v in dims)))
+        if not dims_only:
+            out.update(buckets=buckets, result=result, **dict(zip(("exc_count", "dirty", "items", "heavy", "overflow"), (int(v) for v in counters))))
+        return out
+
     def close(self):
         if self._h:
             self._L.czk_ctx_destroy(self._h)

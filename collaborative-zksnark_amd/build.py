@@ -11,7 +11,9 @@
                      tests/test_sat_arith.py.  The saturated probes are compiled in both forms field.h is built in: with the Montgomery
                      multiply inlined in arith_probe.hip, and with -DCZK_NOINLINE_MUL (the form of pairing.hip, the only one the Fq6 / Fq12
                      tower has) in csrc/lab/sat_probe.hip.  csrc/lab/msm_sort_probe.hip exports czk_lab_msm_sort, which runs the digit sort of
-                     one MSM call (msm_sort.hip) on its own and returns its arrays and dimensions for tests/test_msm_digits.py.  Loaded by tests through Context(lab=True) and by tools through CZK_LIB_PATH;
+                     one MSM call (msm_sort.hip) on its own and returns its arrays and dimensions for tests/test_msm_digits.py; csrc/lab/msm_bucket_probe.hip exports
+                     czk_lab_msm_buckets, which runs the bucket accumulation and reduction (msm.hip's stage bodies) on entry lists the caller wrote and
+                     returns every bucket, the rare-path counters and the lane results for tests/test_msm_buckets.py.  Loaded by tests through Context(lab=True) and by tools through CZK_LIB_PATH;
                      never by the provers.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container as well as on the GPU box.
@@ -37,7 +39,7 @@ SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_
            ("point_ops.hip", ["-DCZK_NOINLINE_MUL"]), ("group_share.hip", ["-DCZK_NOINLINE_MUL"]), ("kzg.hip", ["-DCZK_NOINLINE_MUL"]), ("marlin_index.hip", []), ("plonk_layout.hip", []), ("commit_tree.hip", [])]
 # lab library only: never compiled into, nor linked with, the product library
 LAB_SOURCES = [(os.path.join("lab", "arith_probe.hip"), []), (os.path.join("lab", "sat_probe.hip"), ["-DCZK_NOINLINE_MUL"]),
-               (os.path.join("lab", "msm_sort_probe.hip"), ["-DCZK_NOINLINE_MUL"])]
+               (os.path.join("lab", "msm_sort_probe.hip"), ["-DCZK_NOINLINE_MUL"]), (os.path.join("lab", "msm_bucket_probe.hip"), ["-DCZK_NOINLINE_MUL"])]
 HEADERS = ["field.h", "curve.h", "czk_internal.h", "call.h", "net.h", "sha256.h", "pow_tables.h", "msm_acc.h", "fq2p.h", "fq2pu.h", "fqu.h", "fru.h", "fru_constants.inc", "ntt_pass.h", "te.h", "te_constants.inc", "tower.h", "pairing_constants.inc",
            os.path.join("..", "..", "include", "czk.h")]
 LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h", "arith_probe.h", "sat_probe.h")]

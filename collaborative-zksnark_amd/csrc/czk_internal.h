@@ -618,4 +618,59 @@ void launch_accumulate_g2_u(czk_ctx* ctx, hipStream_t st, const u64* pts, const 
 void launch_accumulate_g2(hipStream_t st, const u64* pts, const u32* sorted, const u32* offsets, const u32* counts, const u32* perm, size_t B,
                           size_t sorted_stride, u64* buckets, unsigned lanes);
 
+// implemented in msm.hip: the launches of the accumulate and reduce stages of one MSM call, without the events around them (msm_stage_accumulate /
+// msm_stage_reduce call them between their waits; the lab's bucket probe, lab/msm_bucket_probe.hip, runs them on one stream).
+constexpr unsigned MSM_L = 8, MSM_LOG_L = 3;   // bucket reduction: buckets per chunk of a level
+// The sizes of a call's bucket / reduction workspace, and its arrays (msm.hip: part of the call's plan and of its buffers)
+struct MsmRedDims {
+    size_t lanes, B, total, lvl0;    // lvl0: entries of the first reduction level
+    int JW, XW;                      // u64 per Jacobian result / per bucket
+    u32 heavy_cap;                   // >= number of 256-entry work items of over-full buckets (msm_acc.h HEAVY_SUB)
+};
+struct MsmRedBufs {
+    u64 *buckets, *lv[4], *result, *tail_scratch, *tail_sums, *heavy_partials;
+    u32 *heavy_items, *heavy_list, *heavy_hdr;
+    uint8_t* dirty;                  // unsaturated kernels: dirty flags + exception list
+};
+inline void msm_red_dims(MsmRedDims& r, bool g1, size_t lanes, size_t B, size_t total) {
+    r.lanes = lanes, r.B = B, r.total = total;
+    r.JW = g1 ? GT<Fq>::JW : GT<Fq2>::JW;   // results leave as Jacobian; buckets are XYZZ internally
+    r.XW = g1 ? GT<Fq>::XW : GT<Fq2>::XW;
+    r.lvl0 = (B + MSM_L - 1) / MSM_L;
+    r.heavy_cap = (u32)(lanes * total / 256 + 64);
+}
+inline size_t msm_red_bytes(const MsmRedDims& r) {
+    return r.lanes * (r.B * r.XW * 8 + 4 * r.lvl0 * r.XW * 8 + r.JW * 8 + r.B + (size_t)12 * 513 * r.XW * 8) + (size_t)r.heavy_cap * (r.XW * 8 + 32) + (1 << 17);
+}
+inline void msm_red_carve(const MsmRedDims& r, char* ws, MsmRedBufs& w) {
+    const size_t lanes = r.lanes, B = r.B;
+    Bump br{ws};
+    w.buckets = br.take<u64>(lanes * B * r.XW);
+    for (int i = 0; i < 4; i++) w.lv[i] = br.take<u64>(lanes * r.lvl0 * r.XW);
+    w.result = br.take<u64>(lanes * r.JW);
+    w.tail_scratch = br.take<u64>(lanes * 12 * 512 * r.XW);   // reduction tail (G1): tree-reduction scratch and the 12 sums
+    w.tail_sums = br.take<u64>(lanes * 12 * r.XW);
+    w.heavy_partials = br.take<u64>((size_t)r.heavy_cap * r.XW);   // over-full buckets: per-chunk partial sums, item / bucket lists, header
+    w.heavy_items = br.take<u32>((size_t)r.heavy_cap * 3);
+    w.heavy_list = br.take<u32>((size_t)r.heavy_cap * 4);
+    w.heavy_hdr = br.take<u32>(4);
+    w.dirty = br.take<uint8_t>(lanes * B + 64 + 3 * 4096 * 4 + 64);
+}
+// What the stage bodies read of a call: the key's arithmetic family, the bucket sets and the table in use.  aff: the lab's batched-affine rounds (rounds != 0).
+struct MsmStageArgs {
+    bool g1, te, unsat;
+    int ub, lean;                    // ub: buckets stay in u-form through the reduction; lean: "msm_reduce_lean"
+    unsigned lanes;
+    size_t B, total;
+    const u64* pts;
+    u32 heavy_cap;
+    const AffArgs* aff;
+};
+// the bucket accumulation kernel (accumulate stream)
+int msm_accumulate_enqueue(czk_ctx* ctx, hipStream_t st, const MsmStageArgs& a, const MsmSortBufs& s, const MsmRedBufs& w);
+// work items of over-full buckets, then the dirty buckets / deferred points of the unsaturated kernels (reduce stream, ahead of the reduction)
+void msm_fixup_enqueue(hipStream_t st, const MsmStageArgs& a, const MsmSortBufs& s, const MsmRedBufs& w);
+// the reduction levels and the tail: w.result holds one Jacobian triple per lane afterwards
+void msm_reduce_enqueue(hipStream_t st, const MsmStageArgs& a, const MsmRedBufs& w);
+
 }  // namespace czk

@@ -1023,9 +1023,21 @@ __device__ __forceinline__ void xyzzu_add(XYZZU& a, const XYZZU& b) {
     for (int i = 0; i < 14; i++) ns1.l[i] = fqu_8p(i) - s1.l[i];
     a.y = fqu_mul_add_s(r, d, ns1, p3);
 }
-// a = 2 a (dbl-2008-s-1, a = 0: 6M + 3S + the fused Y3).  The subgroup has odd order: no point has Y == 0.
+// the complete doubling of curve.h: a point of order two (Y == 0) gives the neutral element, flag set
+__device__ __noinline__ XYZZU xyzzu_double_slow(XYZZU a) { return xyzzu_from_sat(xyzz_double(xyzzu_to_sat(a))); }
+
+// a = 2 a (dbl-2008-s-1, a = 0: 6M + 3S + the fused Y3).  The subgroup has odd order and no point of it has Y == 0, but this family also serves keys
+// that may hold any curve point (CZK_MEM_ANY_POINTS, the one-shot calls), and E(Fq) has three points of order two.  Their doubling through the
+// formulas below would leave zz == 0 under a flag that says finite, and the next addition would run the general formula on it.  Y is normalised and
+// below 4.01 p here (a multiply output, a loaded coordinate, or the 4 p - y of a negated first entry), so it is 0 mod p only if it equals j p with j
+// in 0..4, whose low limb is j (p == 1 mod 2^28): one compare, as in xyzzu_add; the suspicious values (about 2^-25 of all) and every genuine Y == 0
+// go through the saturated complete formulas.
 __device__ __forceinline__ void xyzzu_double(XYZZU& a) {
     if (a.inf) return;
+    if ((a.y.l[0] & FQU_MASK) <= 8u) {
+        a = xyzzu_double_slow(a);
+        return;
+    }
     FqU u;
 #pragma unroll
     for (int i = 0; i < 14; i++) u.l[i] = a.y.l[i] + a.y.l[i];            // U = 2 Y1, limbs < 2^29

@@ -34,25 +34,20 @@
 
 namespace czk {
 
-constexpr unsigned MSM_L = 8, MSM_LOG_L = 3;   // bucket reduction: buckets per chunk of a level
-
 // Everything a call decides before it touches a stream (msm_plan), the options included: the stages branch on these fields.  The head is the sort's view of
 // the call (MsmSortDims): size = pairs that count (variable_base.rs:16), lanes = bucket sets = gridDim.y of every kernel after the digits.
 struct MsmPlan : MsmSortDims {
     const czk_bases* b;
-    size_t lvl0, need_sort, need_red, need_aff, aff_scratch, out_bytes;   // lvl0: entries of the first reduction level
-    u32 heavy_cap;                   // >= number of 256-entry work items of over-full buckets (msm_acc.h HEAVY_SUB)
+    MsmRedDims red;                  // the bucket / reduction workspace (czk_internal.h)
+    size_t need_sort, need_red, need_aff, aff_scratch, out_bytes;
     int lean;                        // "msm_reduce_lean" as this call found it (twisted Edwards reduction kernels, msm_acc.h)
-    int JW, XW, ub;                  // ub: buckets stay in u-form through the reduction (b->te: twisted Edwards tables and buckets, te.h; b->unsat: u-form tables)
+    int ub;                          // buckets stay in u-form through the reduction (b->te: twisted Edwards tables and buckets, te.h; b->unsat: u-form tables)
     bool g1, stable, same, key_valid, may_reuse, any_inf, drop_wait;
     AffArgs aff;                     // lab, batched-affine rounds (rounds != 0): the sizes
 };
 // The arrays of one call, carved from the workspaces of its slot (the sort's: of the slot whose sorted entries it reads) -- msm_carve.
-struct MsmBufs {
+struct MsmBufs : MsmRedBufs {
     MsmSortBufs sort;
-    u64 *buckets, *lv[4], *result, *tail_scratch, *tail_sums, *heavy_partials;
-    u32 *heavy_items, *heavy_list, *heavy_hdr;
-    uint8_t* dirty;                  // unsaturated kernels: dirty flags + exception list
     char* pinned;                    // host staging of the result
     AffArgs aff;
 };
@@ -65,8 +60,6 @@ static int msm_plan(czk_ctx* ctx, const czk_bases* b, const u64* scalars, size_t
     p.stable = stable;
     p.same = same;
     p.g1 = b->group == CZK_G1;
-    p.JW = p.g1 ? GT<Fq>::JW : GT<Fq2>::JW;   // results leave as Jacobian; buckets are XYZZ internally
-    p.XW = p.g1 ? GT<Fq>::XW : GT<Fq2>::XW;
     p.size = b->n < n_scalars ? b->n : n_scalars;
     CZK_TRY(pick_tables(ctx, b, p.size, &p.tv, true));
     // no tables (b->split): the width follows the call, every digit window is a lane of its own with one bucket set (see the head of the file)
@@ -76,11 +69,10 @@ static int msm_plan(czk_ctx* ctx, const czk_bases* b, const u64* scalars, size_t
     msm_sort_dims(p, c, b->split ? msm_num_windows(c) : p.tv.W, b->split, lanes, ctx->msm_affine_rounds == 0, ctx->msm_sort_onepass, ctx->lds_per_block);
     if (p.lanes > 65535) return set_err(ctx, CZK_ERR_SIZE, "too many MSM lanes");
     if ((size_t)p.W * p.nb >= ((size_t)1 << 31)) return set_err(ctx, CZK_ERR_SIZE, "W * n_bases exceeds the 31-bit point index");
-    p.lvl0 = (p.B + MSM_L - 1) / MSM_L;
     p.need_sort = msm_sort_bytes(p);
-    p.heavy_cap = (u32)(p.lanes * p.total / 256 + 64);
-    p.need_red = p.lanes * (p.B * p.XW * 8 + 4 * p.lvl0 * p.XW * 8 + p.JW * 8 + p.B + (size_t)12 * 513 * p.XW * 8) + (size_t)p.heavy_cap * (p.XW * 8 + 32) + (1 << 17);
-    p.out_bytes = p.lanes * p.JW * 8;
+    msm_red_dims(p.red, p.g1, p.lanes, p.B, p.total);
+    p.need_red = msm_red_bytes(p.red);
+    p.out_bytes = p.lanes * p.red.JW * 8;
     p.lean = ctx->msm_reduce_lean;
     p.ub = 1;   // product build: every key's tables are in the unsaturated residue system, buckets stay in u-form through the reduction
 #ifdef CZK_LAB
@@ -125,17 +117,7 @@ static void msm_carve(const MsmPlan& p, const MsmSlot& slot, const MsmSlot& src,
     const size_t lanes = p.lanes, B = p.B;
     MsmSortBufs& s = w.sort;
     msm_sort_carve(p, (char*)src.ws_sort.p, s);
-    Bump br{(char*)slot.ws_red.p};
-    w.buckets = br.take<u64>(lanes * B * p.XW);
-    for (int i = 0; i < 4; i++) w.lv[i] = br.take<u64>(lanes * p.lvl0 * p.XW);
-    w.result = br.take<u64>(lanes * p.JW);
-    w.tail_scratch = br.take<u64>(lanes * 12 * 512 * p.XW);   // reduction tail (G1): tree-reduction scratch and the 12 sums
-    w.tail_sums = br.take<u64>(lanes * 12 * p.XW);
-    w.heavy_partials = br.take<u64>((size_t)p.heavy_cap * p.XW);   // over-full buckets: per-chunk partial sums, item / bucket lists, header
-    w.heavy_items = br.take<u32>((size_t)p.heavy_cap * 3);
-    w.heavy_list = br.take<u32>((size_t)p.heavy_cap * 4);
-    w.heavy_hdr = br.take<u32>(4);
-    w.dirty = br.take<uint8_t>(lanes * B + 64 + 3 * 4096 * 4 + 64);
+    msm_red_carve(p.red, (char*)slot.ws_red.p, w);
     AffArgs& a = w.aff = p.aff;
     if (a.rounds) {   // (lab)
         Bump ba{(char*)slot.ws_aff.p};
@@ -201,80 +183,93 @@ static int msm_stage_sort(czk_ctx* ctx, MsmSlot& slot, bool reuse, const MsmPlan
     return CZK_OK;
 }
 
+static MsmStageArgs stage_args(const MsmPlan& p, const MsmBufs& w) {
+    return MsmStageArgs{p.g1, p.b->te, p.b->unsat, p.ub, p.lean, (unsigned)p.lanes, p.B, p.total, p.tv.pts, p.red.heavy_cap, &w.aff};
+}
+
 // (the unsaturated and twisted Edwards launchers bracket their main kernel with the "msm_accumulate_g{1,2}" profiling scope themselves)
+int msm_accumulate_enqueue(czk_ctx* ctx, hipStream_t sa, const MsmStageArgs& a, const MsmSortBufs& s, const MsmRedBufs& w) {
+    const unsigned lanes = a.lanes;
+    if (a.te) launch_accumulate_g1_te(ctx, sa, a.pts, s.sorted, s.offsets, s.counts, s.perm, a.B, a.total, w.buckets, lanes);
+#ifdef CZK_LAB
+    else if (a.aff && a.aff->rounds) launch_affine_accumulate_g1(ctx, sa, *a.aff, a.pts, s.perm, w.buckets, w.dirty);
+    else if (!a.unsat) {   // saturated tables ("msm_sat"): the round-1 kernels
+        ProfScope ps(ctx, a.g1 ? "msm_accumulate_g1" : "msm_accumulate_g2", sa);
+        (a.g1 ? launch_accumulate_g1 : launch_accumulate_g2)(sa, a.pts, s.sorted, s.offsets, s.counts, s.perm, a.B, a.total, w.buckets, lanes);
+    }
+#else
+    else if (!a.unsat) return set_err(ctx, CZK_ERR_ARG, "bases with saturated window tables: not part of the product build");
+#endif
+    else (a.g1 ? launch_accumulate_g1_u : launch_accumulate_g2_u)(ctx, sa, a.pts, s.sorted, s.offsets, s.counts, s.perm, a.B, a.total, w.buckets, lanes, w.dirty, a.ub);
+    return CZK_OK;
+}
 static int msm_stage_accumulate(czk_ctx* ctx, MsmSlot& slot, const MsmPlan& p, const MsmBufs& w) {
     hipStream_t sa = ctx->s_acc;
-    const MsmSortBufs& s = w.sort;
-    const unsigned lanes = (unsigned)p.lanes;
     CZK_HIP(ctx, hipStreamWaitEvent(sa, slot.ev_sorted, 0));                               // A1
     if (slot.used) CZK_HIP(ctx, hipStreamWaitEvent(sa, slot.ev_red, 0));                   // A2
     ctx->msm_launch_split = p.split;
-    if (p.b->te) launch_accumulate_g1_te(ctx, sa, p.tv.pts, s.sorted, s.offsets, s.counts, s.perm, p.B, p.total, w.buckets, lanes);
-#ifdef CZK_LAB
-    else if (w.aff.rounds) launch_affine_accumulate_g1(ctx, sa, w.aff, p.tv.pts, s.perm, w.buckets, w.dirty);
-    else if (!p.b->unsat) {   // saturated tables ("msm_sat"): the round-1 kernels
-        ProfScope ps(ctx, p.g1 ? "msm_accumulate_g1" : "msm_accumulate_g2", sa);
-        (p.g1 ? launch_accumulate_g1 : launch_accumulate_g2)(sa, p.tv.pts, s.sorted, s.offsets, s.counts, s.perm, p.B, p.total, w.buckets, lanes);
-    }
-#else
-    else if (!p.b->unsat) return set_err(ctx, CZK_ERR_ARG, "bases with saturated window tables: not part of the product build");
-#endif
-    else (p.g1 ? launch_accumulate_g1_u : launch_accumulate_g2_u)(ctx, sa, p.tv.pts, s.sorted, s.offsets, s.counts, s.perm, p.B, p.total, w.buckets, lanes, w.dirty, p.ub);
+    CZK_TRY(msm_accumulate_enqueue(ctx, sa, stage_args(p, w), w.sort, w));
     CZK_HIP(ctx, hipGetLastError());
     CZK_HIP(ctx, hipEventRecord(slot.ev_acc, sa));
     return CZK_OK;
 }
 
-static void launch_reduce_level(hipStream_t sr, const MsmPlan& p, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl, u64* Po, u64* Eo, size_t n_out) {
-    if (!p.g1) launch_reduce_level_g2(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, (unsigned)p.lanes, p.ub);
-    else if (p.ub) launch_reduce_level_g1_u(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, (unsigned)p.lanes, p.b->te, p.lean);
+static void launch_reduce_level(hipStream_t sr, const MsmStageArgs& a, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl, u64* Po, u64* Eo, size_t n_out) {
+    if (!a.g1) launch_reduce_level_g2(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, a.lanes, a.ub);
+    else if (a.ub) launch_reduce_level_g1_u(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, a.lanes, a.te, a.lean);
 #ifdef CZK_LAB
-    else launch_reduce_level_g1(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, (unsigned)p.lanes);
+    else launch_reduce_level_g1(sr, P, E, n_in, MSM_L, scale_dbl, Po, Eo, n_out, a.lanes);
 #endif
 }
 // the end of the reduction, n_in <= 1024 entries per lane: latency-bound from here, so bit-sum tree reductions instead of more levels (one entry: a conversion)
-static void launch_reduce_end(hipStream_t sr, const MsmPlan& p, const MsmBufs& w, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl) {
-    const unsigned lanes = (unsigned)p.lanes;
-    if (!p.g1) n_in > 1 ? launch_reduce_tail_g2(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes, p.ub) : launch_finish_g2(sr, P, E, lanes, w.result, p.ub);
-    else if (p.ub) n_in > 1 ? launch_reduce_tail_g1_u(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes, p.b->te, p.lean) : launch_finish_g1_u(sr, P, E, lanes, w.result, p.b->te);
+static void launch_reduce_end(hipStream_t sr, const MsmStageArgs& a, const MsmRedBufs& w, const u64* P, const u64* E, size_t n_in, unsigned scale_dbl) {
+    const unsigned lanes = a.lanes;
+    if (!a.g1) n_in > 1 ? launch_reduce_tail_g2(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes, a.ub) : launch_finish_g2(sr, P, E, lanes, w.result, a.ub);
+    else if (a.ub) n_in > 1 ? launch_reduce_tail_g1_u(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes, a.te, a.lean) : launch_finish_g1_u(sr, P, E, lanes, w.result, a.te);
 #ifdef CZK_LAB
     else n_in > 1 ? launch_reduce_tail_g1(sr, P, E, n_in, scale_dbl, w.tail_scratch, w.tail_sums, w.result, lanes) : launch_finish_g1(sr, P, E, lanes, w.result);
 #endif
+}
+// work items beyond the first 1024 entries of over-full buckets (none with uniformly random scalars), then the dirty buckets / deferred points of the
+// unsaturated kernels (normally none): on the reduce stream, so the accumulate stream goes straight on
+void msm_fixup_enqueue(hipStream_t sr, const MsmStageArgs& a, const MsmSortBufs& s, const MsmRedBufs& w) {
+    const unsigned lanes = a.lanes;
+    if (a.te) launch_heavy_g1_te(sr, a.pts, s.sorted, s.offsets, s.counts, a.B, a.total, w.buckets, lanes, w.heavy_hdr, w.heavy_items, w.heavy_list, w.heavy_partials, a.heavy_cap);
+    else (a.g1 ? launch_heavy_g1 : launch_heavy_g2)(sr, a.pts, s.sorted, s.offsets, s.counts, a.B, a.total, w.buckets, lanes, a.unsat ? w.dirty : nullptr, w.heavy_hdr,
+                                                    w.heavy_items, w.heavy_list, w.heavy_partials, a.heavy_cap, a.unsat ? 1 : 0, a.ub);
+    if (a.unsat && !a.te) {
+#ifdef CZK_LAB
+        if (a.aff && a.aff->rounds) launch_accumulate_g1_u_fixup_lvl(sr, a.pts, s.sorted, s.offsets, s.counts, a.B, a.total, w.buckets, lanes, w.dirty, a.aff->lvl[(a.aff->rounds - 1) & 1]);
+        else
+#endif
+        (a.g1 ? launch_accumulate_g1_u_fixup : launch_accumulate_g2_u_fixup)(sr, a.pts, s.sorted, s.offsets, s.counts, a.B, a.total, w.buckets, lanes, w.dirty, a.ub);
+    }
+}
+void msm_reduce_enqueue(hipStream_t sr, const MsmStageArgs& a, const MsmRedBufs& w) {
+    const u64 *P = w.buckets, *E = nullptr;
+    size_t n_in = a.B;
+    unsigned level = 0;
+    for (; n_in > 1024; level++) {   // chunked running sums: MSM_L entries per chunk, the chunk offsets folded in at the next level
+        const size_t n_out = (n_in + MSM_L - 1) / MSM_L;
+        u64 *Po = w.lv[(level & 1) * 2], *Eo = w.lv[(level & 1) * 2 + 1];
+        launch_reduce_level(sr, a, P, E, n_in, level * MSM_LOG_L, Po, Eo, n_out);
+        P = Po;
+        E = Eo;
+        n_in = n_out;
+    }
+    launch_reduce_end(sr, a, w, P, E, n_in, level * MSM_LOG_L);
 }
 // `borrowed`: the slot whose sort this call read, when it is not its own
 static int msm_stage_reduce(czk_ctx* ctx, MsmSlot& slot, MsmSlot* borrowed, const MsmPlan& p, const MsmBufs& w) {
     hipStream_t sr = ctx->s_red;
     CZK_HIP(ctx, hipStreamWaitEvent(sr, p.drop_wait ? slot.ev_sorted : slot.ev_acc, 0));   // R1 (R1': the broken schedule)
-    const MsmSortBufs& s = w.sort;
-    const unsigned lanes = (unsigned)p.lanes;
-    // work items beyond the first 1024 entries of over-full buckets (none with uniformly random scalars), then the dirty buckets / deferred points of the
-    // unsaturated kernels (normally none): on the reduce stream, so the accumulate stream goes straight on
-    if (p.b->te) launch_heavy_g1_te(sr, p.tv.pts, s.sorted, s.offsets, s.counts, p.B, p.total, w.buckets, lanes, w.heavy_hdr, w.heavy_items, w.heavy_list, w.heavy_partials, p.heavy_cap);
-    else (p.g1 ? launch_heavy_g1 : launch_heavy_g2)(sr, p.tv.pts, s.sorted, s.offsets, s.counts, p.B, p.total, w.buckets, lanes, p.b->unsat ? w.dirty : nullptr, w.heavy_hdr,
-                                                    w.heavy_items, w.heavy_list, w.heavy_partials, p.heavy_cap, p.b->unsat ? 1 : 0, p.ub);
-    if (p.b->unsat && !p.b->te) {
-#ifdef CZK_LAB
-        if (w.aff.rounds) launch_accumulate_g1_u_fixup_lvl(sr, p.tv.pts, s.sorted, s.offsets, s.counts, p.B, p.total, w.buckets, lanes, w.dirty, w.aff.lvl[(w.aff.rounds - 1) & 1]);
-        else
-#endif
-        (p.g1 ? launch_accumulate_g1_u_fixup : launch_accumulate_g2_u_fixup)(sr, p.tv.pts, s.sorted, s.offsets, s.counts, p.B, p.total, w.buckets, lanes, w.dirty, p.ub);
-    }
+    const MsmStageArgs a = stage_args(p, w);
+    msm_fixup_enqueue(sr, a, w.sort, w);
     CZK_HIP(ctx, hipEventRecord(slot.ev_fix, sr));
     if (borrowed) CZK_HIP(ctx, hipEventRecord(borrowed->ev_fix, sr));
     {
         ProfScope ps(ctx, "msm_reduce", sr);
-        const u64 *P = w.buckets, *E = nullptr;
-        size_t n_in = p.B;
-        unsigned level = 0;
-        for (; n_in > 1024; level++) {   // chunked running sums: MSM_L entries per chunk, the chunk offsets folded in at the next level
-            const size_t n_out = (n_in + MSM_L - 1) / MSM_L;
-            u64 *Po = w.lv[(level & 1) * 2], *Eo = w.lv[(level & 1) * 2 + 1];
-            launch_reduce_level(sr, p, P, E, n_in, level * MSM_LOG_L, Po, Eo, n_out);
-            P = Po;
-            E = Eo;
-            n_in = n_out;
-        }
-        launch_reduce_end(sr, p, w, P, E, n_in, level * MSM_LOG_L);
+        msm_reduce_enqueue(sr, a, w);
     }
     CZK_HIP(ctx, hipGetLastError());
     chaos_point(ctx, sr);

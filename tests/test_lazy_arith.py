@@ -361,6 +361,36 @@ def test_xyzzu_add_and_double_with_exceptional_cases(ctx):
     for g, A in zip(got[::9], pts):
         assert xyzz_affine(rows_of(g[:56])) == pyref.ec_add(F, A, A)
     assert run(ctx, "xyzzu_double", [zero + [1]])[0][56] == 1
+    # points of order two, (-1, 0) and (-zeta, 0): Y == 0 at every representative j p the discipline admits (y <= 4 p) gives the neutral element, flag
+    # set -- the family serves keys that may hold any curve point (CZK_MEM_ANY_POINTS); and a false alarm, a real point whose Y has a low limb below
+    # the filter's bound, still doubles to the right point through the complete formulas
+    zeta = next(z for z in (pow(g, (P - 1) // 3, P) for g in range(2, 20)) if z != 1)
+    for T in ((P - 1, 0), (-zeta % P, 0)):
+        assert pyref.ec_on_curve(pyref.F1, T, 1)
+        rows = []
+        for j in range(5):
+            z = rng.randrange(1, P)
+            rows.append([u(T[0] * z * z, j), FQ.digits(j * P), u(z * z), u(z ** 3)] + [0])
+        for g in run(ctx, "xyzzu_double", rows):
+            assert g[56] == 1
+    alarm, n3 = [], (P - 1) // 3                               # 9 does not divide p - 1: a cube c has the cube root c^(1 / 3 mod (p - 1) / 3)
+    assert n3 % 3
+    while len(alarm) < 3:
+        x = rng.randrange(P)
+        y = fq_sqrt((x ** 3 + 1) % P)
+        if y is None:
+            continue
+        Yv = (rng.randrange(1, 1 << 340) << 28) + 4 * len(alarm)      # the integer Y = y z^3 R' is to be: not 0 mod p, low limb 0, 4, 8
+        c = Yv * pow(y * FQ.one, -1, P) % P
+        if pow(c, n3, P) != 1:
+            continue                                               # z^3 = c has no solution
+        z = pow(c, pow(3, -1, n3), P)
+        assert pow(z, 3, P) == c
+        row = xyzz_rep((x, y), z)
+        assert FQ.value(row[1]) == Yv and row[1][0] <= 8
+        alarm.append((row + [0], pyref.ec_add(F, (x, y), (x, y))))
+    for g, (_, s) in zip(run(ctx, "xyzzu_double", [r for r, _ in alarm]), alarm):
+        assert g[56] == 0 and xyzz_affine(rows_of(g[:56])) == s
 
 
 def jac_affine(words):
