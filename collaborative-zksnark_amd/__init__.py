@@ -18,3 +18,4 @@ from . import keyio  # noqa: F401
 from . import kzg  # noqa: F401
 from . import marlin  # noqa: F401
 from . import plonk  # noqa: F401
+from . import fri  # noqa: F401

@@ -297,6 +297,13 @@ class Context:
             out[name] = a[:, :out[k]]
         return out
 
+    def lab_merkle_commit(self, a: int, lanes: int, n: int, stride: int, tree: int, tree_stride: int):
+        """czk_lab_merkle_commit (csrc/lab/merkle_probe.hip, lab library only): czk_fr_merkle_commit's tree in the form that was not shipped, on device
+        pointers; only enqueues.  Raises unless the context was opened with lab=True."""
+        if not self._lab:
+            raise RuntimeError("lab_merkle_commit needs Context(lab=True): libczk_hip.so does not export czk_lab_merkle_commit")
+        self._ck(self._L.czk_lab_merkle_commit(self._h, _ptr(a), C.c_size_t(lanes), C.c_size_t(n), C.c_size_t(stride), _ptr(tree), C.c_size_t(tree_stride)))
+
     def lab_msm_buckets(self, bases: "Bases", B: int, sorted_, offsets, counts, perm, dims_only: bool = False):
         """czk_lab_msm_buckets (csrc/lab/msm_bucket_probe.hip, lab library only): the bucket accumulation, the over-full-bucket and fix-up
         kernels and the bucket reduction of one MSM call on entry lists the caller wrote, over the tables of a registered key.  sorted_:
@@ -802,6 +809,89 @@ class Context:
             out_stride = out.shape[1] if lanes else n
         self._ck(self._L.czk_fr_gather(self._h, _ptr(src if lanes and n else None), C.c_size_t(src_len), C.c_size_t(src_stride), C.c_size_t(lanes),
                                      _ptr(index if lanes and n else None), C.c_size_t(n), _ptr(out if lanes and n else None), C.c_size_t(out_stride), C.c_int(mem)))
+        return out
+
+    # ---- the reference's Merkle commitment of share vectors (com.rs ComField) and the FRI fold ------------------------------------
+    def fr_merkle_commit(self, a, lanes: int = 1, n=None, stride=None, tree=None, tree_stride=None, roots=True, mem=CZK_MEM_HOST):
+        """czk_fr_merkle_commit: every lane's binary SHA-256 tree over n Montgomery Fr.  Host mode: a is (lanes, stride, 4) limbs of which n (default
+        stride) per lane are hashed, `tree` an optional (lanes, tree_stride, 32) uint8 array whose digests past 2n - 1 stay; returns (tree, roots) with
+        roots (lanes, 32) uint8.  Device mode: pointers with n, stride and tree_stride given; returns (tree, roots), roots None -- and the call only
+        enqueued -- with roots=False."""
+        if mem == CZK_MEM_HOST:
+            a = np.ascontiguousarray(a, np.uint64).reshape(lanes, -1, 4) if lanes else np.zeros((0, 0, 4), dtype=np.uint64)
+            stride = a.shape[1] if lanes else (n or 0)
+            n = stride if n is None else n
+            if tree is None:
+                tree = np.zeros((lanes, max(2 * n - 1, 0), 32), dtype=np.uint8)
+            assert tree.dtype == np.uint8 and tree.flags.c_contiguous and tree.shape[0] == lanes
+            tree_stride = tree.shape[1] if tree_stride is None else tree_stride
+        out = np.zeros((lanes, 32), dtype=np.uint8) if roots else None
+        live = lanes and n and not n & (n - 1)     # otherwise the library returns before it reads a pointer
+        self._ck(self._L.czk_fr_merkle_commit(self._h, _ptr(a if live else None), C.c_size_t(lanes), C.c_size_t(n), C.c_size_t(stride),
+                                              _ptr(tree if live else None), C.c_size_t(tree_stride), _ptr(out if roots and lanes else None), C.c_int(mem)))
+        return tree, out
+
+    def fr_merkle_open(self, a, tree, idx, lanes: int = 1, n=None, stride=None, tree_stride=None, q=None, out_shares=None, out_paths=None,
+                       mem=CZK_MEM_HOST):
+        """czk_fr_merkle_open: shares (q, lanes, 4) and sibling paths (q, lanes, log2 n, 32) at the q indices.  Host mode: a (lanes, stride, 4), tree
+        (lanes, tree_stride, 32) and idx as numpy arrays (n defaults to stride); returns (shares, paths).  Device mode: pointers and every size given."""
+        if mem == CZK_MEM_HOST:
+            a = np.ascontiguousarray(a, np.uint64).reshape(lanes, -1, 4) if lanes else np.zeros((0, 0, 4), dtype=np.uint64)
+            tree = np.ascontiguousarray(tree, np.uint8).reshape(lanes, -1, 32) if lanes else np.zeros((0, 0, 32), dtype=np.uint8)
+            idx = np.ascontiguousarray(idx, np.uint64).reshape(-1)
+            stride, q = a.shape[1] if lanes else (n or 0), idx.size
+            n = stride if n is None else n
+            tree_stride = (tree.shape[1] if lanes else max(2 * n - 1, 0)) if tree_stride is None else tree_stride
+            log_n = max(n.bit_length() - 1, 0)
+            out_shares = np.zeros((q, lanes, 4), dtype=np.uint64)
+            out_paths = np.zeros((q, lanes, log_n, 32), dtype=np.uint8)
+        live = lanes and q
+        nonempty = lambda x: None if x is None or (isinstance(x, np.ndarray) and x.size == 0) else x   # noqa: E731
+        self._ck(self._L.czk_fr_merkle_open(self._h, _ptr(nonempty(a) if live else None), C.c_size_t(lanes), C.c_size_t(n), C.c_size_t(stride),
+                                            _ptr(nonempty(tree) if live else None), C.c_size_t(tree_stride), _ptr(idx if live else None), C.c_size_t(q),
+                                            _ptr(nonempty(out_shares)), _ptr(nonempty(out_paths)), C.c_int(mem)))
+        return out_shares, out_paths
+
+    def fr_merkle_verify(self, roots, idx, shares, paths, n: int, values=None, lanes=None, q=None, ok=None, mem=CZK_MEM_HOST):
+        """czk_fr_merkle_verify: (ok, bad) with ok[query] = 1 when every lane's share hashes up its path to the lane's root and, with `values`, the
+        lanes' shares sum to values[query]; bad = the number of zeros.  Host mode: roots (lanes, 32), idx (q,), shares (q, lanes, 4), paths (q, lanes,
+        log2 n, 32), values (q, 4) as numpy arrays, ok returned as a (q,) uint8 array.  Device mode: pointers, with lanes, q and an `ok` buffer given."""
+        if mem == CZK_MEM_HOST:
+            roots = np.ascontiguousarray(roots, np.uint8).reshape(-1, 32)
+            idx = np.ascontiguousarray(idx, np.uint64).reshape(-1)
+            lanes, q = roots.shape[0], idx.size
+            shares = np.ascontiguousarray(shares, np.uint64)
+            paths = np.ascontiguousarray(paths, np.uint8)
+            log_n = max(n.bit_length() - 1, 0)
+            if shares.size != q * lanes * 4 or paths.size != q * lanes * log_n * 32:
+                raise ValueError("shares must hold q x lanes elements and paths q x lanes x log2(n) digests")
+            if values is not None:
+                values = np.ascontiguousarray(values, np.uint64)
+                if values.size != 4 * q:
+                    raise ValueError("values must hold q elements")
+            ok = np.zeros(q, dtype=np.uint8)
+        bad = C.c_size_t(0)
+        nonempty = lambda x: None if x is None or (isinstance(x, np.ndarray) and x.size == 0) else x   # noqa: E731
+        self._ck(self._L.czk_fr_merkle_verify(self._h, _ptr(nonempty(roots)), C.c_size_t(lanes), C.c_size_t(n), _ptr(nonempty(idx)), C.c_size_t(q),
+                                              _ptr(nonempty(shares)), _ptr(nonempty(paths)), _ptr(nonempty(values)), _ptr(nonempty(ok)), C.byref(bad),
+                                              C.c_int(mem)))
+        return ok, bad.value
+
+    def fri_fold(self, f, alpha, lanes: int = 1, n=None, stride=None, out=None, out_stride=None, mem=CZK_MEM_HOST):
+        """czk_fr_fri_fold: out[l][j] = f[l][2j] + alpha f[l][2j+1], j < n / 2; alpha (4,) Montgomery limbs on the host.  Host mode: f (lanes, stride, 4)
+        (n defaults to stride), `out` an optional (lanes, out_stride, 4) array whose elements past n / 2 stay; returns out.  Device mode: pointers."""
+        alpha = np.ascontiguousarray(alpha, np.uint64).reshape(4)
+        if mem == CZK_MEM_HOST:
+            f = np.ascontiguousarray(f, np.uint64).reshape(lanes, -1, 4) if lanes else np.zeros((0, 0, 4), dtype=np.uint64)
+            stride = f.shape[1] if lanes else (n or 0)
+            n = stride if n is None else n
+            if out is None:
+                out = np.zeros((lanes, n // 2, 4), dtype=np.uint64)
+            assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape[0] == lanes
+            out_stride = out.shape[1] if lanes else n // 2
+        live = lanes and n >= 2
+        self._ck(self._L.czk_fr_fri_fold(self._h, _ptr(f if live else None), C.c_size_t(lanes), C.c_size_t(n), C.c_size_t(stride), _ptr(alpha),
+                                         _ptr(out if live else None), C.c_size_t(out_stride), C.c_int(mem)))
         return out
 
     def poly_div_linear(self, coeffs, z, lanes: int = 1, n=None, quotient=None, remainder=None, mem=CZK_MEM_HOST):

@@ -13,6 +13,7 @@
 // Montgomery conversion), not by the loads: measured, EXPERIMENTS.md section 24.
 #include "call.h"
 #include "sha256.h"
+#include "sha256_dev.h"
 
 using namespace czk;
 
@@ -23,33 +24,6 @@ static_assert(E >= 8 && (E & (E - 1)) == 0 && F >= 8 && (F & (F - 1)) == 0, "lea
 struct Sha256State {
     u32 h[8];
 };
-
-__device__ const u32 SHA_K[64] = {
-    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u, 0x243185beu,
-    0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau,
-    0x5cb0a9dcu, 0x76f988dau, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u, 0x27b70a85u,
-    0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u, 0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u,
-    0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu,
-    0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-
-__device__ __forceinline__ u32 rotr(u32 x, int n) { return __builtin_rotateright32(x, n); }
-
-// one compression (FIPS 180-4 section 6.2.2) with the 16-word rolling schedule: w[i & 15] is overwritten in place, every index is a constant
-// after unrolling, so the schedule and the working variables live in registers
-__device__ __forceinline__ void sha256_block(u32 (&st)[8], u32 (&w)[16]) {
-    u32 a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-#pragma unroll
-    for (int i = 0; i < 64; i++) {
-        if (i >= 16) {
-            const u32 w15 = w[(i + 1) & 15], w2 = w[(i + 14) & 15];
-            w[i & 15] += (rotr(w15, 7) ^ rotr(w15, 18) ^ (w15 >> 3)) + w[(i + 9) & 15] + (rotr(w2, 17) ^ rotr(w2, 19) ^ (w2 >> 10));
-        }
-        const u32 t1 = h + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + SHA_K[i] + w[i & 15];
-        const u32 t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-        h = g, g = f, f = e, e = d + t1, d = c, c = b, b = a, a = t1 + t2;
-    }
-    st[0] += a, st[1] += b, st[2] += c, st[3] += d, st[4] += e, st[5] += f, st[6] += g, st[7] += h;
-}
 
 // item k of a hash's input as eight big-endian words: a leaf's k-th element (Montgomery -> canonical, limbs byte-swapped) or a node's k-th child digest
 template <bool LEAF>

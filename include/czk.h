@@ -678,6 +678,41 @@ int czk_plonk_layout(czk_ctx* ctx, const uint32_t* succ, size_t n_gates, size_t 
  * blocks.  CZK_MEM_DEVICE: the call only enqueues on the context's stream; an index >= src_len writes 0, and nothing outside the arrays is accessed. */
 int czk_fr_gather(czk_ctx* ctx, const uint64_t* src, size_t src_len, size_t src_stride, size_t lanes, const uint32_t* index, size_t n,
                   uint64_t* out, size_t out_stride, int mem);
+
+/* The reference's vector commitment of shared values, ComField (mpc-algebra/src/com.rs), and the fold of its FRI commit phase (mpc-snarks/src/client.rs
+ * :739-842), for share lanes that all live on one GPU (merkle.hip).  Linear in the shares: a lane is whatever the caller passes (an additive share, the sh
+ * lane of SPDZ, a Shamir evaluation); no call looks at a MAC.  The bytes are the reference's:
+ *   bytes(v) = into_repr() as 32 little-endian bytes (czk_fr_vec_serialize's);  leaf_i = SHA256(bytes(a[i]));  node = SHA256(left || right); no tags, no
+ *   length prefix.  A TREE of n = 2^k leaves is 2n - 1 digests of 32 bytes (digest order) per lane, level by level: level 0 = the n leaf hashes at digest
+ *   offset 0, level 1 at offset n, level L (n >> L digests) at offset 2n - 2 (n >> L), the root at offset 2n - 2.  The reference's Key is these levels
+ *   without the root.  A PATH for index i is k digests: tree[level][(i >> level) ^ 1] for level = 0 .. k - 1 (the reference's OpeningProof holds one per
+ *   party).  n = 1 is valid: the tree is the one leaf hash and every path is empty.
+ * Common rules.  CZK_ERR_SIZE, before any pointer is read: n zero or not a power of two (the fold: n < 2, any other n is taken), stride < n,
+ * tree_stride < 2n - 1, a byte count that overflows.  lanes = 0 or q = 0: CZK_OK, nothing is touched.  Device pointers to elements and trees are 16-byte aligned (digests a caller
+ * passes as roots or paths: 4-byte).
+ * czk_fr_merkle_commit (ComField::commit, com.rs:36-67): a = `lanes` vectors of n Montgomery Fr, `stride` elements apart; tree: lane l at tree + 32 l
+ *   tree_stride bytes; roots32: lanes x 32 bytes in HOST memory, or NULL.  Reads a[l][0..n) only and writes digests [0, 2n - 1) of tree[l] only.  With
+ *   CZK_MEM_DEVICE and roots32 == NULL the call only enqueues on the context's stream; otherwise it blocks for the roots.
+ * czk_fr_merkle_open (open_at, :68-94): idx = q uint64 indices in `mem`; out_shares[query][lane] = a[lane][idx[query]] (q x lanes Montgomery Fr),
+ *   out_paths[query][lane][level] (q x lanes x log2 n x 32 bytes) = the path above.  CZK_MEM_HOST: CZK_ERR_ARG for an index >= n; blocks.
+ *   CZK_MEM_DEVICE: only enqueues; an index >= n writes zero shares and zero paths and reads nothing outside the arrays.
+ * czk_fr_merkle_verify (check_opening, :95-123): roots = lanes x 32 bytes, idx, shares, paths as the open wrote them, values = q Montgomery Fr or NULL,
+ *   ok = q bytes, all in `mem`; out_bad: HOST.  Per (query, lane) the share is hashed and walked up its path, bit j of the index putting the sibling left
+ *   or right at level j, and the result compared with roots[lane]; per query, with values != NULL, the lanes' shares must sum to values[query] mod r.
+ *   ok[query] = 1 or 0 and *out_bad = the number of zeros.  Blocks (the count's read-back).  An index >= n: CZK_ERR_ARG with CZK_MEM_HOST, a bad query
+ *   with CZK_MEM_DEVICE.
+ * czk_fr_fri_fold (client.rs:767-771): out[l][j] = f[l][2j] + alpha f[l][2j+1] for j < n / 2 (rounded down); elements [n / 2, out_stride) of a lane
+ *   are not written.
+ *   alpha: one Montgomery Fr in HOST memory.  out may not overlap f (CZK_ERR_ARG where the call can tell).  CZK_MEM_DEVICE: only enqueues. */
+int czk_fr_merkle_commit(czk_ctx* ctx, const uint64_t* a, size_t lanes, size_t n, size_t stride, uint8_t* tree, size_t tree_stride, uint8_t* roots32,
+                         int mem);
+int czk_fr_merkle_open(czk_ctx* ctx, const uint64_t* a, size_t lanes, size_t n, size_t stride, const uint8_t* tree, size_t tree_stride,
+                       const uint64_t* idx, size_t q, uint64_t* out_shares, uint8_t* out_paths, int mem);
+int czk_fr_merkle_verify(czk_ctx* ctx, const uint8_t* roots, size_t lanes, size_t n, const uint64_t* idx, size_t q, const uint64_t* shares,
+                         const uint8_t* paths, const uint64_t* values, uint8_t* ok, size_t* out_bad, int mem);
+int czk_fr_fri_fold(czk_ctx* ctx, const uint64_t* f, size_t lanes, size_t n, size_t stride, const uint64_t* alpha, uint64_t* out, size_t out_stride,
+                    int mem);
+
 /* DensePolynomial / (X - z): KZG10::compute_witness_polynomial (poly-commit/src/kzg10/mod.rs:200-224; shares divide
  * lane-wise because the divisor is public, mpc-algebra/src/share/add.rs:148-156).  coeffs: lanes x n Fr, low degree
  * first; quotient: lanes x (n-1) Fr; remainder (may be NULL): lanes Fr = p(z), which is also

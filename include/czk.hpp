@@ -845,6 +845,62 @@ inline std::vector<Fr> fr_gather(const Context& ctx, const std::vector<Fr>& src,
     return out;
 }
 
+// ComField (mpc-algebra/src/com.rs:25-124) for every party's lane at once: the binary SHA-256 trees of `lanes` vectors of n Montgomery Fr, `stride`
+// elements apart, in `mem` (czk_fr_merkle_commit / _open / _verify, czk.h).  The tree and the roots live on the host; the vectors may live on the device.
+struct MerkleTree {
+    size_t lanes = 0, n = 0;
+    std::vector<uint8_t> tree;    // lanes x (2n - 1) digests, level by level (the reference's Key is every level but the last)
+    std::vector<uint8_t> roots;   // lanes x 32 bytes in lane order (the reference's Commitment: party 1's root, then party 0's)
+    struct Opening {
+        std::vector<uint64_t> idx;
+        std::vector<Fr> shares;        // q x lanes
+        std::vector<uint8_t> paths;    // q x lanes x log2 n x 32 bytes
+    };
+    static MerkleTree commit(const Context& ctx, const uint64_t* a, size_t lanes, size_t n, size_t stride, int mem) {
+        if (!n || (n & (n - 1))) throw Panic(CZK_ERR_SIZE, "assertion failed: hashes.len().is_power_of_two()");
+        MerkleTree t;
+        t.lanes = lanes, t.n = n;
+        t.tree.assign(lanes * (2 * n - 1) * 32, 0);
+        t.roots.assign(lanes * 32, 0);
+        if (!lanes) return t;
+        if (mem == CZK_MEM_HOST) ctx.check(czk_fr_merkle_commit(ctx.raw(), a, lanes, n, stride, t.tree.data(), 2 * n - 1, t.roots.data(), mem));
+        else {   // device vectors: the tree is built next to them and comes down once
+            DeviceLanes d(ctx, lanes, 2 * n - 1);
+            ctx.check(czk_fr_merkle_commit(ctx.raw(), a, lanes, n, stride, reinterpret_cast<uint8_t*>(d.data()), 2 * n - 1, t.roots.data(), mem));
+            for (size_t l = 0; l < lanes; l++)
+                ctx.check(czk_lanes_download(ctx.raw(), d.raw(), l, 0, reinterpret_cast<uint64_t*>(t.tree.data() + l * (2 * n - 1) * 32), 2 * n - 1));
+        }
+        return t;
+    }
+    // open_at (com.rs:68-94) at every index; a: the committed vectors in HOST memory
+    Opening open_at(const Context& ctx, const uint64_t* a, size_t stride, const std::vector<uint64_t>& idx) const {
+        unsigned log_n = 0;
+        while (((size_t)1 << log_n) < n) log_n++;
+        Opening o{idx, std::vector<Fr>(idx.size() * lanes, Fr{{0, 0, 0, 0}}), std::vector<uint8_t>(idx.size() * lanes * log_n * 32, 0)};
+        if (idx.empty() || !lanes) return o;
+        ctx.check(czk_fr_merkle_open(ctx.raw(), a, lanes, n, stride, tree.data(), 2 * n - 1, idx.data(), idx.size(), o.shares[0].l,
+                                     o.paths.empty() ? nullptr : o.paths.data(), CZK_MEM_HOST));
+        return o;
+    }
+    // check_opening (com.rs:95-123) for every index: true when every path leads to its root and (values non-null: q Fr) the shares sum to the values
+    static bool check_opening(const Context& ctx, const std::vector<uint8_t>& roots, size_t n, const Opening& o, const Fr* values = nullptr,
+                              std::vector<uint8_t>* ok = nullptr) {
+        const size_t lanes = roots.size() / 32, q = o.idx.size();
+        std::vector<uint8_t> flags(q, 0);
+        size_t bad = 0;
+        if (q && lanes)
+            ctx.check(czk_fr_merkle_verify(ctx.raw(), roots.data(), lanes, n, o.idx.data(), q, o.shares[0].l, o.paths.empty() ? nullptr : o.paths.data(),
+                                           values ? values[0].l : nullptr, flags.data(), &bad, CZK_MEM_HOST));
+        if (ok) *ok = flags;
+        return bad == 0;
+    }
+};
+
+// f_next[i] = f[2i] + alpha f[2i+1] (mpc-snarks/src/client.rs:767-771) on `lanes` vectors of n Montgomery Fr in `mem`; out may not overlap f
+inline void fri_fold(const Context& ctx, const uint64_t* f, size_t lanes, size_t n, size_t stride, const Fr& alpha, uint64_t* out, size_t out_stride, int mem) {
+    ctx.check(czk_fr_fri_fold(ctx.raw(), f, lanes, n, stride, alpha.l, out, out_stride, mem));
+}
+
 // mpc-snarks/src/groth/r1cs_to_qap.rs:47-113 -- the NTT / pointwise sequence of witness_map for a single prover
 // (T = Fr).  `a`, `b`, `c` are the evaluated constraint rows (a[0..N), then the instance copy; :67-83, :95-100).
 // `batch_product` is F::batch_product_in_place (:92) -- a plain product here, the Beaver protocol for shares.

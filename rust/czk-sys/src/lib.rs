@@ -185,6 +185,10 @@ extern "C" {
     pub fn czk_marlin_arithmetize(ctx: *mut czk_ctx, row_ptr: *const u64, col_idx: *const u32, coeff: *const u64, m: usize, nnz: usize, log_h: c_uint, log_x: c_uint, n_instance: usize, k: usize, out: *mut u64, mem: c_int) -> c_int;
     pub fn czk_plonk_layout(ctx: *mut czk_ctx, succ: *const u32, n_gates: usize, n_prods: usize, w_evals: *mut u64, s_evals: *mut u64, mem: c_int) -> c_int;
     pub fn czk_fr_gather(ctx: *mut czk_ctx, src: *const u64, src_len: usize, src_stride: usize, lanes: usize, index: *const u32, n: usize, out: *mut u64, out_stride: usize, mem: c_int) -> c_int;
+    pub fn czk_fr_merkle_commit(ctx: *mut czk_ctx, a: *const u64, lanes: usize, n: usize, stride: usize, tree: *mut u8, tree_stride: usize, roots32: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_fr_merkle_open(ctx: *mut czk_ctx, a: *const u64, lanes: usize, n: usize, stride: usize, tree: *const u8, tree_stride: usize, idx: *const u64, q: usize, out_shares: *mut u64, out_paths: *mut u8, mem: c_int) -> c_int;
+    pub fn czk_fr_merkle_verify(ctx: *mut czk_ctx, roots: *const u8, lanes: usize, n: usize, idx: *const u64, q: usize, shares: *const u64, paths: *const u8, values: *const u64, ok: *mut u8, out_bad: *mut usize, mem: c_int) -> c_int;
+    pub fn czk_fr_fri_fold(ctx: *mut czk_ctx, f: *const u64, lanes: usize, n: usize, stride: usize, alpha: *const u64, out: *mut u64, out_stride: usize, mem: c_int) -> c_int;
     pub fn czk_poly_div_linear(ctx: *mut czk_ctx, coeffs: *const u64, n: usize, lanes: usize, z: *const u64, quotient: *mut u64, remainder: *mut u64, mem: c_int) -> c_int;
     pub fn czk_poly_evaluate(ctx: *mut czk_ctx, coeffs: *const u64, n: usize, lanes: usize, z: *const u64, values: *mut u64, mem: c_int) -> c_int;
     pub fn czk_poly_evaluate_many(ctx: *mut czk_ctx, count: usize, coeffs: *const *const u64, n: *const usize, lanes: *const usize, z: *const u64, values: *const *mut u64) -> c_int;
