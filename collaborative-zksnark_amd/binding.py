@@ -48,6 +48,7 @@ def _share_material_counts(L, op: int, n: int):
 CZK_GSZ_OP_MUL, CZK_GSZ_OP_INV, CZK_GSZ_OP_PARTIAL_PRODUCTS, CZK_GSZ_OP_PRODUCT_CHECK = 0, 1, 2, 3   # czk_gsz_material_counts
 CZK_GSZ_GROUP_OP_MUL, CZK_GSZ_GROUP_OP_PRODUCT_CHECK = 0, 1   # czk_gsz_group_material_counts
 CZK_GSZ_DN_DOUBLES, CZK_GSZ_DN_RANDS = 0, 1  # czk_gsz_dn_*: the same value under degree d and 2 d / degree d only
+CZK_FQ12_OP_MUL, CZK_FQ12_OP_DIV, CZK_FQ12_OP_INV = 0, 1, 2   # czk_fq12_vec_op
 
 
 def open_commit_flags(commit) -> int:
@@ -704,6 +705,47 @@ class Context:
                                                    _ptr(zs_ptr), _ptr(zs_inf_ptr), C.c_size_t(n), _ptr(gr_ptr), _ptr(gr_inf_ptr), _ptr(gr2_ptr), _ptr(gr2_inf_ptr),
                                                    _ptr(fr_ptr), _ptr(fr2_ptr), _ptr(rands_ptr), C.byref(ok), C.byref(bad)))
         return bool(ok.value), bad.value
+
+    # ---- pairings of shared points and multiplicative target-group shares on device lanes (czk.h; csrc/pairing_share.hip) -----------------------
+    @staticmethod
+    def _mac_limbs(mac_shares, parties):
+        ms = None if mac_shares is None else np.ascontiguousarray(mac_shares, np.uint64).reshape(-1, 4)
+        assert ms is None or ms.shape[0] >= parties
+        return ms
+
+    def share_pairing(self, lpp: int, parties: int, mac_shares, a_ptr, a_inf_ptr, b_ptr, b_inf_ptr, tx_ptr, tx_inf_ptr, ty_ptr, ty_inf_ptr, tz_ptr, out_ptr, n: int):
+        """czk_share_pairing: a, tx are lpp * parties device lanes of n affine G1 points, b, ty of G2 points (+ as many infinity bytes each, or None), tz and
+        out as many lanes of n Fq12 (72 u64); mac_shares (parties, 4) Montgomery limbs (None for lpp = 1).  Points are assumed to lie in the prime-order
+        subgroups.  Returns the number of elements whose MAC checks failed."""
+        bad = C.c_uint64(0)
+        self._ck(self._L.czk_share_pairing(self._h, C.c_size_t(lpp), C.c_size_t(parties), _ptr(self._mac_limbs(mac_shares, parties)), _ptr(a_ptr), _ptr(a_inf_ptr),
+                                         _ptr(b_ptr), _ptr(b_inf_ptr), _ptr(tx_ptr), _ptr(tx_inf_ptr), _ptr(ty_ptr), _ptr(ty_inf_ptr), _ptr(tz_ptr), _ptr(out_ptr),
+                                         C.c_size_t(n), C.byref(bad)))
+        return bad.value
+
+    def gt_share_open(self, lpp: int, parties: int, mac_shares, v_ptr, n: int, out_ptr):
+        """czk_gt_share_open: out (n x 72, device) = the product of the sh lanes of v -> the number of elements whose MAC check failed"""
+        bad = C.c_uint64(0)
+        self._ck(self._L.czk_gt_share_open(self._h, C.c_size_t(lpp), C.c_size_t(parties), _ptr(self._mac_limbs(mac_shares, parties)), _ptr(v_ptr), C.c_size_t(n),
+                                         _ptr(out_ptr), C.byref(bad)))
+        return bad.value
+
+    def gt_share_scale(self, lpp: int, parties: int, mac_shares, v_ptr, f_ptr, out_ptr, n: int):
+        """czk_gt_share_scale: out = the lanes v scaled by the public f (n x 72, device); v_ptr None: from_public(f).  Only enqueues."""
+        self._ck(self._L.czk_gt_share_scale(self._h, C.c_size_t(lpp), C.c_size_t(parties), _ptr(self._mac_limbs(mac_shares, parties)), _ptr(v_ptr), _ptr(f_ptr),
+                                          _ptr(out_ptr), C.c_size_t(n)))
+
+    def fq12_vec_op(self, op: int, a, b=None, n=None, out=None, mem: int = CZK_MEM_HOST):
+        """czk_fq12_vec_op: elementwise CZK_FQ12_OP_MUL / _DIV / _INV on n Fq12 (the inverse of zero is zero).  Host mode takes (n, 72) uint64 arrays and
+        returns one; in device mode a, b, out are device pointers and n the count."""
+        if mem == CZK_MEM_HOST:
+            a = np.ascontiguousarray(a, np.uint64).reshape(-1, 72)
+            n = a.shape[0]
+            b = None if b is None else np.ascontiguousarray(b, np.uint64).reshape(n, 72)
+            out = np.zeros((n, 72), dtype=np.uint64)
+        z = lambda x: x if n else None   # noqa: E731
+        self._ck(self._L.czk_fq12_vec_op(self._h, C.c_int(op), _ptr(z(a)), _ptr(z(b)), _ptr(z(out)), C.c_size_t(n), C.c_int(mem)))
+        return out
 
     # ---- the GSZ material made on the device (czk.h; csrc/gsz_dn.hip) -----------------------------------------------------------------------
     def fr_random(self, key: bytes, nonce: bytes, first: int, n: int, out=None, mem=CZK_MEM_HOST):

@@ -555,6 +555,8 @@ int points_sum_device(czk_ctx* ctx, int group, const u64* pts, const uint8_t* in
 // implemented in pairing.hip: is_one[j] = the product of pairings over pairs [offs_host[j], offs_host[j + 1]) is one (device buffers; blocking)
 int pairing_is_one_device(czk_ctx* ctx, const u64* g1, const uint8_t* g1_inf, const u64* g2, const uint8_t* g2_inf, const size_t* offs_host, size_t k,
                           uint8_t* is_one);
+// implemented in pairing.hip: G2Prepared::from (k_g2_prepare) of n DEVICE points (q_inf may be null), line j of point t at lines[(36 j + w) n + t]; only enqueues
+void g2_prepare_enqueue(czk_ctx* ctx, const u64* q_aff, const uint8_t* q_inf, size_t n, u64* lines);
 void launch_reduce_level_g1(hipStream_t st, const u64* P, const u64* E, size_t n_in, unsigned L, unsigned scale_dbl, u64* Po, u64* Eo, size_t n_out,
                             unsigned lanes);
 // (G2: `ub` = buckets and level arrays in u-form, reduced on fq2pu.h's unsaturated lane pairs)

@@ -659,9 +659,18 @@ class Groth16Local:
 #   group_doubles(prover, group, n) -> (gr, gr_inf, gr2, gr2_inf)     GSZ: one random point under degree t (gr) and under 2 t (gr2) in the exponent
 #   field_doubles(prover, n)        -> (fr, fr2)                      GSZ: the field's double shares, (P, n, 4)
 #   rands(prover, n)                -> (P, n, 4)                      GSZ: random shares of degree t
+#   pairing_triples(prover, n)      -> (tx, tx_inf, ty, ty_inf, tz)   additive / SPDZ (pairing_share.py): tx (L, n, 12) G1 points, ty (L, n, 24) G2 points, tz (L, n, 72)
+#                                                                     Fq12 shared MULTIPLICATIVELY, the product of tz's sh lanes = e(open tx, open ty)
 def _dev(a):
     a = np.ascontiguousarray(a)
     return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
+
+
+def fq12_one() -> np.ndarray:
+    """the one of Fq12, (72,) uint64 Montgomery limbs in tower.h's layout"""
+    one = np.zeros(72, np.uint64)
+    one[:6] = to_mont_limbs_fq(1)
+    return one
 
 
 def _infinity(group_aw: int, L: int, n: int):
@@ -694,6 +703,12 @@ class DummyGroupSource:
     def rands(self, p, n):
         return _dev(np.tile(to_mont_limbs([1])[0], (p.lanes, n, 1)))
 
+    def pairing_triples(self, p, n):
+        """DummyPairingTripleSource (mpc-algebra/src/wire/pairing.rs:44-58): x = y = infinity, z = e(x, y) = one on every lane"""
+        x, x_inf = _infinity(12, p.lanes, n)
+        y, y_inf = _infinity(24, p.lanes, n)
+        return x, x_inf, y, y_inf, _dev(np.tile(fq12_one(), (p.lanes, n, 1)))
+
 
 class SeededGroupDealer:
     """Random group triples, group doubles, field doubles and random shares from a seed: the values are drawn and shared on the host (the prover's
@@ -723,6 +738,18 @@ class SeededGroupDealer:
 
     def rands(self, p, n):
         return self._scalars(p, [self.rng.randrange(1, R_MOD) for _ in range(n)], p.gsz_t)
+
+    def pairing_triples(self, p, n):
+        """x = [u] G1 and y = [v] G2 additively shared; z shared multiplicatively: lane l is e([w_l] G1, G2) for an additive sharing w of u v (the mac lanes
+        carry the key times those exponents), so the product of the sh lanes is e(x, y)"""
+        czk, ctx = p.czk, p.ctx
+        u, v = [self.rng.randrange(R_MOD) for _ in range(n)], [self.rng.randrange(R_MOD) for _ in range(n)]
+        tx, tx_inf = p.lift_lanes(czk.CZK_G1, self._scalars(p, u))
+        ty, ty_inf = p.lift_lanes(czk.CZK_G2, self._scalars(p, v))
+        w, w_inf = p.lift_lanes(czk.CZK_G1, self._scalars(p, [a * b % R_MOD for a, b in zip(u, v)]))
+        g2 = ctx.fixed_base_points(czk.CZK_G2, np.array([[1, 0, 0, 0]], np.uint64))[0]
+        tz = ctx.pairing(w.cpu().numpy().view(np.uint64).reshape(-1, 12), np.tile(g2.reshape(1, 24), (p.lanes * n, 1)), g1_inf=w_inf.cpu().numpy().reshape(-1))
+        return tx, tx_inf, ty, ty_inf, _dev(tz.reshape(p.lanes, n, 72))
 
 
 class DnGroupSource:

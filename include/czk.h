@@ -557,6 +557,67 @@ int czk_gsz_group_batch_mul(czk_ctx* ctx, int group, size_t parties, unsigned de
                             const uint64_t* gr, const uint8_t* gr_inf, const uint64_t* gr2, const uint8_t* gr2_inf, uint64_t* out, uint8_t* out_inf, size_t n,
                             uint64_t* out_bad);
 
+/* ---- pairings of a SHARED G1 point with a SHARED G2 point; multiplicative target-group shares (mpc-algebra/src/wire/pairing.rs, share/add.rs, share/spdz.rs) -- */
+/* MpcPairingEngine::pairing (wire/pairing.rs:194-229) through a pairing triple, and the shares it yields: MulFieldShare (share/add.rs:407-480) and
+ * SpdzMulFieldShare (share/spdz.rs:459-541) in Fq12 -- what the reference's PairingDh / PairingProd / PairingDiv computations run on
+ * (mpc-snarks/src/client.rs:503-581).  Lanes form only: every party's lanes on this GPU, in czk_share_group_batch_scale's lane order: lpp = 1
+ * additive shares, lpp = 2 SPDZ shares (lane 2 p = party p's sh, lane 2 p + 1 = its mac), L = lpp parties lanes, at most 32 parties.  mac_shares:
+ * one Montgomery Fr per party, HOST, any key (NULL allowed for lpp = 1).  Every other array is CZK_MEM_DEVICE on the context's GPU (czk_fq12_vec_op
+ * takes `mem`).
+ *   a G1 / G2 vector        L lanes of n affine Montgomery points (12 / 24 u64 each), lanes n points apart, plus L n infinity bytes in the same order.
+ *                           An infinity array may be NULL: no point of it is infinity.
+ *   a target-group vector   L lanes of n Fq12 (72 u64 each: c0.c0.c0, c0.c0.c1, c0.c1.c0, ... c1.c2.c1, each Fq 6 Montgomery limbs), lanes n
+ *                           elements apart.  The shares are MULTIPLICATIVE: the value is the product of the sh lanes, the mac lanes multiply to
+ *                           value^key.
+ * SUBGROUP ASSUMPTION: as for czk_share_group_batch_scale, every point is assumed to lie in the prime-order subgroup; the calls do not check it.
+ *
+ * czk_share_pairing: a, b: the shared G1 / G2 operands; (tx, ty, tz): n pairing triples, tx in G1, ty in G2, tz in Fq12, the product of tz's sh
+ * lanes = e(open tx, open ty).  With xa = open(a + tx) and yb = open(b + ty) (the sums of the sh lanes) the reference computes
+ * z / e(xa, y) / e(x, yb) * e(xa, yb) (pairing.rs:225), the last factor scaled into the share (spdz.rs:500-506, add.rs:444-449).  Here
+ *     out_l = tz_l * FE( ML( (-xa, ty_l), (-tx_l, yb), ([k_l] xa, yb) ) )   k_l = 1 on the king's sh lane (lane 0), mac_share_j on party j's mac lane,
+ *                                                                           0 elsewhere (the third pair is then left out)
+ * -- one Miller loop over two or three pairs, one final exponentiation and one Fq12 product per (lane, element); the same field element, limb for
+ * limb, since negating the G1 point inverts a pairing value and e(P, Q)^k = e([k] P, Q) in the prime-order subgroup.  Pairs with an infinite member
+ * are skipped (algebra/ec/src/models/bls12/mod.rs:99-103): xa, yb, tx_l, ty_l may all be infinity.  The lanes of out open to e(open a, open b).
+ * *out_bad (host): the elements where a MAC check fails: [key] xa - (the sum of the mac lanes of a + tx) is not infinity, or the same for yb in G2
+ * (key = the sum of the mac shares mod r; an element counts once).  Always 0 for lpp = 1.  A changed mac lane of tz is not seen here: it travels
+ * into out's mac lane and czk_gt_share_open counts it.
+ * Three kernels -- the open (one thread per (element, slot), one double-and-add chain deep), G2Prepared::from over the (L + 1) n points ty_l and yb,
+ * the product of pairings (one thread per (lane, element)) -- none separated by a host synchronisation; one read-back of the count (the call blocks).
+ *
+ * czk_gt_share_open: reveal (add.rs:414-416, spdz.rs:469-478): out_i (n x 72) = the product of the sh lanes of v.  For SPDZ the element is counted in
+ * *out_bad unless x^A * (the product of the mac lanes)^(-1) is one, A = the INTEGER sum of the canonical mac shares (not reduced mod r): the verdict
+ * of the reference's prod_j x^(mac_share_j) / mac_j for any x, inside the order-r subgroup or not.  The reference asserts; here it is a count.
+ *
+ * czk_gt_share_scale: scale by the public f (n x 72) (spdz.rs:500-506, add.rs:444-449): lane 0 is multiplied by f_i, party j's mac lane by
+ * f_i^(mac_share_j), the other lanes are copied.  v = NULL is from_public (spdz.rs:479-485, add.rs:417-421): the lanes start at one.  Only enqueues.
+ *
+ * czk_fq12_vec_op: out_i = a_i b_i (CZK_FQ12_OP_MUL), a_i / b_i (CZK_FQ12_OP_DIV) or 1 / a_i (CZK_FQ12_OP_INV, b ignored) on flat arrays of n Fq12 in
+ * `mem`; device memory: only enqueues.  The lane-wise mul / inv of multiplicative shares (add.rs:455-479) is exactly this on L n elements.  A zero
+ * divisor yields ZERO (the inversion is Fermat's at the bottom of the tower); the reference panics there.
+ *
+ * Deliberate differences from the reference:
+ *   (a) its SPDZ mul / batch_mul of multiplicative shares drop their products (spdz.rs:512-528: the by-value mul results are never assigned); here both
+ *       lanes are multiplied, as the additive form does;
+ *   (b) pairing() builds the mac of e(xa, y) from the process-global stand-in key (from_add_shared, spdz.rs:486-492); here it is e(xa, mac lane of y),
+ *       which needs no key;
+ *   (c) with only one operand shared the reference reveals both (pairing.rs:226-228); pair the public point with every lane through czk_pairing
+ *       instead -- by bilinearity the lanes are shares of the pairing and nothing is revealed.
+ * GSZ pairing shares are commented out in the reference (mpc-algebra/src/lib.rs:56-62) and are not built.
+ *
+ * n = 0 or parties = 0: CZK_OK, nothing touched but *out_bad.  NULL ctx / out_bad, lpp not 1 or 2, more than 32 parties, an unknown op or mem, NULL
+ * vectors with work to do (mac_shares for lpp = 2 included): CZK_ERR_ARG.  More outputs than one launch covers (2^36 threads): CZK_ERR_SIZE.  `out`
+ * must not overlap an input.  Workspace: the staging pool (czk_fq12_vec_op from host memory: per-call allocations). */
+#define CZK_FQ12_OP_MUL 0
+#define CZK_FQ12_OP_DIV 1
+#define CZK_FQ12_OP_INV 2
+int czk_share_pairing(czk_ctx* ctx, size_t lpp, size_t parties, const uint64_t* mac_shares, const uint64_t* a, const uint8_t* a_inf, const uint64_t* b,
+                      const uint8_t* b_inf, const uint64_t* tx, const uint8_t* tx_inf, const uint64_t* ty, const uint8_t* ty_inf, const uint64_t* tz,
+                      uint64_t* out, size_t n, uint64_t* out_bad);
+int czk_gt_share_open(czk_ctx* ctx, size_t lpp, size_t parties, const uint64_t* mac_shares, const uint64_t* v, size_t n, uint64_t* out, uint64_t* out_bad);
+int czk_gt_share_scale(czk_ctx* ctx, size_t lpp, size_t parties, const uint64_t* mac_shares, const uint64_t* v, const uint64_t* f, uint64_t* out, size_t n);
+int czk_fq12_vec_op(czk_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, int mem);
+
 /* ---- GSZ material made on the device: a keyed generator of field elements, Damgard-Nielsen dealing and extraction, its consistency check ---- */
 /* czk_fr_random: a keyed stream of field elements.  Element i comes from the ChaCha20 block (RFC 8439 block function, 20 rounds, 32-bit block counter) at
  * (key, nonce, counter = first + i): lo = bytes 0..31 of the block as a little-endian integer reduced mod 2^252, hi = bytes 32..63 likewise,

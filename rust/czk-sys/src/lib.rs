@@ -87,6 +87,9 @@ pub const CZK_GSZ_OP_PARTIAL_PRODUCTS: c_int = 2; // #define
 pub const CZK_GSZ_OP_PRODUCT_CHECK: c_int = 3; // #define
 pub const CZK_GSZ_GROUP_OP_MUL: c_int = 0; // #define
 pub const CZK_GSZ_GROUP_OP_PRODUCT_CHECK: c_int = 1; // #define
+pub const CZK_FQ12_OP_MUL: c_int = 0; // #define
+pub const CZK_FQ12_OP_DIV: c_int = 1; // #define
+pub const CZK_FQ12_OP_INV: c_int = 2; // #define
 
 #[link(name = "czk_hip")]
 extern "C" {
@@ -167,6 +170,10 @@ extern "C" {
     pub fn czk_gsz_group_product_check(ctx: *mut czk_ctx, group: c_int, parties: usize, degree: c_uint, xs: *const u64, ys: *const u64, ys_inf: *const u8, zs: *const u64, zs_inf: *const u8, n: usize, gr: *const u64, gr_inf: *const u8, gr2: *const u64, gr2_inf: *const u8, fr: *const u64, fr2: *const u64, rands: *const u64, out_ok: *mut u64, out_bad: *mut u64) -> c_int;
     pub fn czk_share_group_batch_scale(ctx: *mut czk_ctx, group: c_int, lpp: usize, parties: usize, mac_shares: *const u64, s: *const u64, s_inf: *const u8, o: *const u64, tx: *const u64, tx_inf: *const u8, ty: *const u64, tz: *const u64, tz_inf: *const u8, out: *mut u64, out_inf: *mut u8, n: usize, out_bad: *mut u64) -> c_int;
     pub fn czk_gsz_group_batch_mul(ctx: *mut czk_ctx, group: c_int, parties: usize, degree: c_uint, x: *const u64, y: *const u64, y_inf: *const u8, gr: *const u64, gr_inf: *const u8, gr2: *const u64, gr2_inf: *const u8, out: *mut u64, out_inf: *mut u8, n: usize, out_bad: *mut u64) -> c_int;
+    pub fn czk_share_pairing(ctx: *mut czk_ctx, lpp: usize, parties: usize, mac_shares: *const u64, a: *const u64, a_inf: *const u8, b: *const u64, b_inf: *const u8, tx: *const u64, tx_inf: *const u8, ty: *const u64, ty_inf: *const u8, tz: *const u64, out: *mut u64, n: usize, out_bad: *mut u64) -> c_int;
+    pub fn czk_gt_share_open(ctx: *mut czk_ctx, lpp: usize, parties: usize, mac_shares: *const u64, v: *const u64, n: usize, out: *mut u64, out_bad: *mut u64) -> c_int;
+    pub fn czk_gt_share_scale(ctx: *mut czk_ctx, lpp: usize, parties: usize, mac_shares: *const u64, v: *const u64, f: *const u64, out: *mut u64, n: usize) -> c_int;
+    pub fn czk_fq12_vec_op(ctx: *mut czk_ctx, op: c_int, a: *const u64, b: *const u64, out: *mut u64, n: usize, mem: c_int) -> c_int;
     pub fn czk_fr_random(ctx: *mut czk_ctx, key: *const u8, nonce: *const u8, first: u32, n: usize, out: *mut u64, mem: c_int) -> c_int;
     pub fn czk_gsz_dn_counts(kind: c_int, parties: usize, degree: c_uint, want: usize, deal: *mut usize, outputs: *mut usize) -> c_int;
     pub fn czk_gsz_dn_generate(ctx: *mut czk_ctx, kind: c_int, parties: usize, degree: c_uint, keys: *const u8, nonce: *const u8, deal: usize, out_r: *mut u64, out_r2: *mut u64) -> c_int;
