@@ -34,7 +34,7 @@ LIB_LAB = os.path.join(HERE, "libczk_hip_lab.so")
 # (source, extra flags).  msm.hip (the pipeline), msm_sort.hip (the digit sort) and msm_bases.hip (keys, window tables, setup kernels) are built with the Montgomery
 # multiply out of line (see field.h CZK_NOINLINE_MUL); the hot kernels keep it inlined.  core.hip is host code only (the host-side
 # group operations): out of line too, 14 s instead of 4.5 min of host compilation.
-SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_MUL"]), ("ntt.hip", []), ("ntt_pass.hip", []), ("ntt_mixed.hip", []), ("msm.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_sort.hip", ["-DCZK_NOINLINE_MUL"]),
+SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_MUL"]), ("ntt.hip", []), ("ntt_pass.hip", []), ("ntt_mixed.hip", []), ("fr_vec.hip", []), ("witness_map.hip", []), ("msm.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_sort.hip", ["-DCZK_NOINLINE_MUL"]),
            ("msm_bases.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_acc_g1.hip", []),
            ("msm_acc_g2.hip", []), ("msm_red_g2.hip", []), ("msm_heavy_g2.hip", []), ("poly.hip", []), ("share.hip", []), ("share_mul.hip", []), ("gsz_mul.hip", []), ("gsz_dn.hip", []), ("net.hip", ["-DCZK_NOINLINE_MUL"]), ("net_rounds.hip", ["-DCZK_NOINLINE_MUL"]),
            ("pairing.hip", ["-DCZK_NOINLINE_MUL"]), ("fixed_base.hip", []), ("point_codec.hip", ["-DCZK_NOINLINE_MUL"]),

@@ -114,7 +114,7 @@ Sha256State tag_state(const char* tag) {
     return r;
 }
 
-constexpr unsigned BLOCKS_PER_CU = 8;   // grid cap of the three kernels, as the pointwise Fr kernels' (ntt.hip grid_for)
+constexpr unsigned BLOCKS_PER_CU = 8;   // grid cap of the three kernels, as the pointwise Fr kernels' (fr_vec.hip fr_grid)
 unsigned grid_cap(czk_ctx* ctx, size_t items) {   // blocks of 256 threads for a grid-stride loop over `items`
     const size_t max_blocks = (size_t)ctx->num_cu * BLOCKS_PER_CU;
     if (items >= max_blocks * 256) return (unsigned)max_blocks;

@@ -160,7 +160,7 @@ struct czk_ctx {
     bool msm_sat = false, msm_sat_g2 = false;   // lab "msm_sat" / "msm_sat_g2": keys registered from now on keep saturated tables and accumulate kernels
     bool msm_no_te = false;          // lab "msm_no_te": G1 keys registered from now on keep the XYZZ kernels (what CZK_MEM_ANY_POINTS does per key)
     long net_create_timeout_ms = 0;  // "net_create_timeout_ms": how long czk_net_create on this context waits for its peers (0 = the communicator's default, 120 s)
-    unsigned long long* open_bad = nullptr;   // device counter of czk_fr_spdz_open (allocated once)
+    unsigned long long* open_bad = nullptr;   // device counter of czk_fr_spdz_open (fr_vec.hip; allocated once)
     unsigned long long* share_cnt = nullptr;  // device counters of the shared-value protocols (share_mul.hip): [0] failed MAC checks, [1] zero divisors
     // lab "chaos": schedule perturbation (tests/test_chaos.py).  Non-zero = seed: every stage boundary (the profiling brackets around the sort / accumulate /
     // reduce / NTT / polynomial stages, the result copy) first enqueues a spin kernel of random length on the stage's stream and / or sleeps on the host, and the
@@ -170,7 +170,7 @@ struct czk_ctx {
     bool ntt_skip_coset_first = false;   // lab "ntt_skip_coset_first": timing experiment (wrong results), see ntt.hip
     unsigned long long chaos = 0;
     int chaos_drop_wait = 0;
-    bool ntt_fuse_pairs = false;     // "ntt_fuse_pairs": the witness map's ifft -> coset_fft pairs share a pass where their tiles line up (ntt.hip ifft_coset_fft_device);
+    bool ntt_fuse_pairs = false;     // "ntt_fuse_pairs": the witness map's ifft -> coset_fft pairs share a pass where their tiles line up (witness_map.hip ifft_coset_fft_device);
                                      // measured + 0.5 % per Groth16 proof (EXPERIMENTS.md section 14), below the 1 % adoption bar: off by default
     uint8_t witness_map_short = 7;   // "witness_map_short", a bit set: 1 = czk_witness_map_post_h transforms c once, 2 = czk_witness_map_pre_masked adds on the transforms' last store,
                                      // 4 = czk_spdz_open_combine is one kernel; a clear bit = the same values from the kernel sequence of before (EXPERIMENTS.md section 22)
@@ -400,7 +400,11 @@ int gsz_dn_extract_launch(czk_ctx* ctx, int kind, size_t parties, unsigned degre
 size_t gsz_dn_combine_ws(czk_ctx* ctx, size_t lanes, size_t outputs);   // workspace, in elements
 int gsz_dn_combine_launch(czk_ctx* ctx, size_t lanes, const u64* r, const u64* r2, size_t stride, size_t outputs, const u64* coin, u64* ws, u64* u);
 int gsz_dn_verdict_launch(czk_ctx* ctx, const u64* opened);             // opened[0] != opened[1] -> ctx->share_cnt[1] = 1
-// implemented in ntt.hip
+// implemented in fr_vec.hip: the two pointwise kernels the transform and the witness map launch (device buffers; only enqueue on ctx->stream, at the grid of the
+// pointwise entry points, and leave hipGetLastError to the caller)
+void fr_vec_op_launch(czk_ctx* ctx, int op, const u64* a, const u64* b, u64* out, size_t n);                   // out = a op b (czk_binop)
+void fr_sub_scale_launch(czk_ctx* ctx, const u64* ab, const u64* c, const Fr& k, u64* out, size_t n);          // out = (ab - c) k
+// implemented in ntt.hip (its internal interface, the pass plan and ensure_tables: ntt_pass.h)
 // `addend` (lanes x D canonical Fr, not the lanes being transformed) rides on the last pass's store: a coset inverse transform writes
 // (coset_ifft(data) - addend) * *scale, a forward or coset forward transform writes its output + addend (scale unused).  Same values as the pointwise kernels.
 int ntt_device(czk_ctx* ctx, u64* data, unsigned log_d, size_t lanes, int kind, size_t in_len, const u64* src = nullptr, size_t src_stride = 0,

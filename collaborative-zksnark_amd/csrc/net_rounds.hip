@@ -1,6 +1,6 @@
 // net_rounds.hip -- the MPC rounds on a communicator (net.h): the reference's commit-then-open round, its batch opens and its shared-value protocols with one
 // party per communicator, each as a single call on device lanes.  Host code only (the kernels it launches live in share.hip / share_mul.hip / gsz_mul.hip /
-// gsz_dn.hip / commit_tree.hip / ntt.hip); every byte crosses the wire through the communicator's exchanges (net.hip).
+// gsz_dn.hip / commit_tree.hip / fr_vec.hip); every byte crosses the wire through the communicator's exchanges (net.hip).
 //
 //   reference                                                            here
 //   MpcSerNet::atomic_broadcast     mpc-algebra/src/channel.rs:50-75      czk_net_atomic_broadcast

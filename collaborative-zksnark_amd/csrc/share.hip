@@ -5,7 +5,7 @@
 //       values = sum of the broadcast `sh` lanes                          -> czk_fr_lanes_sum
 //       dx_t   = mac_share * value - mac (what goes into atomic_broadcast) -> czk_fr_spdz_dx
 //       assert(sum of the broadcast dx_t == 0)                            -> czk_fr_lanes_sum (counts non-zero sums)
-//     (czk_fr_spdz_open in ntt.hip is the one-kernel form for the case where all parties' lanes share this GPU.)
+//     (czk_fr_spdz_open in fr_vec.hip is the one-kernel form for the case where all parties' lanes share this GPU.)
 //   * GSZ / Shamir batch_open (mpc-algebra/src/share/gsz20/mod.rs:286-300, 434-466): party j holds p(w^j) for the order-n
 //     root w of MixedRadixEvaluationDomain::new(n_parties) (algebra/poly/src/domain/mixed_radix.rs:57-107, root rule
 //     algebra/ff/src/fields/mod.rs:337-386 with SMALL_SUBGROUP_BASE = 3); open = size-n inverse DFT of the broadcast values,

@@ -22,7 +22,7 @@ BLOCK = 256               # threads per block of every capped grid-stride launch
 # file (under collaborative-zksnark_amd/csrc) -> the caps `cap = (size_t)ctx->num_cu * K` in source order: (line, K, kernels launched under it)
 GRID_CAPS = {
     "share.hip": [(52, 8, ("k_lanes_sum", "k_spdz_dx", "k_gsz_open"))],
-    "ntt.hip": [(280, 8, ("k_vec_op", "k_vec_scale", "k_vec_scale_dev", "k_beaver", "k_spdz_open", "k_repr", "k_sub_scale"))],
+    "fr_vec.hip": [(78, 8, ("k_vec_op", "k_vec_scale", "k_vec_scale_dev", "k_beaver", "k_spdz_open", "k_repr", "k_sub_scale", "k_spdz_open_combine"))],
     "poly.hip": [(381, 16, ("k_r1cs_matvec",)), (562, 16, ("k_lincomb",))],
     "lanes.hip": [(234, 16, ("k_copy_3d",))],
     "ntt_mixed.hip": [(150, 16, ("k_mixed_split", "k_mixed_combine"))],

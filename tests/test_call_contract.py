@@ -7,7 +7,9 @@ tests/pairing_ref.py, the codec of tests/point_codec_ref.py and, for the KZG ver
 logarithms (tests/test_kzg.py); never from the library.
 The matrix is run whole: tests/test_point_ops.py, test_fixed_base.py, test_point_codec.py, test_pairing.py and test_kzg.py cover the cell "host
 memory, every optional array given" at sizes that cross a block too, but not at exactly these, and the cell costs milliseconds here.  fq_sqrt,
-whose outputs are all required, is run in device memory only (host memory: tests/test_point_codec.py, n up to 257)."""
+whose outputs are all required, is run in device memory only (host memory: tests/test_point_codec.py, n up to 257).
+The last section does the same for the pointwise Fr calls (csrc/fr_vec.hip: values from Python integers, n = 1 and 257) and pins the rejections and
+empty calls of the radix-2 transforms (csrc/ntt.hip) and of the Groth16 witness map (csrc/witness_map.hip)."""
 import ctypes as C
 
 import numpy as np
@@ -44,8 +46,22 @@ ABI = {
     "czk_kzg10_vk_create": ("g gamma_g h beta_h out", "ppppp"),
     "czk_kzg10_check": ("vk comm comm_inf points values w w_inf random_v k out_ok mem", "ppppppppzpi"),
     "czk_kzg10_batch_check": ("vk comm comm_inf points values w w_inf random_v randomizers offsets b out_ok mem", "ppppppppppzpi"),
+    # the pointwise Fr calls (fr_vec.hip), the radix-2 transforms (ntt.hip) and the Groth16 witness map (witness_map.hip)
+    "czk_fr_vec_op": ("op a b out n mem", "ipppzi"),
+    "czk_fr_vec_scale": ("a k out n mem", "pppzi"),
+    "czk_fr_beaver_combine": ("x y z sx oy add_open out n mem", "pppppipzi"),
+    "czk_fr_spdz_open": ("shares parties n out_value out_bad", "pzzpp"),
+    "czk_fr_into_repr": ("a out n mem", "ppzi"),
+    "czk_fr_from_repr": ("a out n mem", "ppzi"),
+    "czk_spdz_open_combine": ("a b tx ty tz parties king_mask sx oy chk_a chk_b ab n", "pppppzqpppppz"),
+    "czk_ntt_fr": ("data log_d lanes kind in_len mem", "puzizi"),
+    "czk_ntt_fr_to": ("src src_stride dst log_d lanes kind in_len mem", "pzpuzizi"),
+    "czk_witness_map_pre": ("a a_len b b_len log_d lanes", "pzpzuz"),
+    "czk_witness_map_pre_masked": ("a a_len b b_len mask_a mask_b log_d lanes", "pzpzppuz"),
+    "czk_witness_map_post": ("ab c c_len log_d lanes", "ppzuz"),
+    "czk_witness_map_post_h": ("ab c c_len log_d lanes", "ppzuz"),
 }
-_CT = {"i": C.c_int, "u": C.c_uint, "z": C.c_size_t}
+_CT = {"i": C.c_int, "u": C.c_uint, "z": C.c_size_t, "q": C.c_uint64}
 
 
 def _ptr(x):
@@ -585,3 +601,203 @@ def test_unaligned_device_byte_buffer(ctx, good, name, arg):
     kw, room = dict(good[DEV][name]), Mem(ctx, DEV).out(64, np.uint8)
     kw[arg] = room.data_ptr() + 1
     assert call(ctx, name, **kw) == (ERR_ARG, "device byte buffers must be 8-byte aligned")
+
+
+# ------------------------------------------------------------------------------------------------- fr_vec.hip, ntt.hip, witness_map.hip
+# The pointwise Fr calls, the radix-2 transforms and the Groth16 witness map.  Values of the transforms and of the witness map are covered by
+# tests/test_gpu_parity.py and tests/test_witness_map_short.py; here: the pointwise values for every kind of caller, and every rejection.
+# (A null context: tests/test_fr_ntt_calls_cpu.py.)
+ERR_SIZE, SCALAR_HOST = 1, 256
+FR_SIZES = (1, 257)                            # one element; one past the 256-thread block
+FR_ROWS = 258                                  # rows [1, 1 + n) are used
+LOG_D, D = 3, 8                                # the domain of the transform and witness-map rejections
+SCALE_MEM_MSG = "mem must be CZK_MEM_HOST, CZK_MEM_DEVICE or CZK_MEM_DEVICE | CZK_MEM_SCALAR_HOST"
+ADICITY_MSG = "domain larger than 2^TWO_ADICITY (radix2/mod.rs:61-63)"
+WM_NULL_MSG, WM_SIZE_MSG = "null witness_map argument", "witness_map: more evaluations than the domain holds"
+
+
+@pytest.fixture(scope="module")
+def fr_rows():
+    """five columns of FR_ROWS residues: 0, 1 and r - 1 meet each other and random elements in every column pair (periods 4, 5, 7, 9, 11)"""
+    from util import limbs_to_ints, rand_fr_canonical
+    rnd = limbs_to_ints(rand_fr_canonical(0xC0DE, 5 * FR_ROWS))
+    edge = (0, None, 1, R_MOD - 1)             # row 1, the only row of n = 1, is random in every column
+    cols = []
+    for c, period in enumerate((4, 5, 7, 9, 11)):
+        cols.append([rnd[c * FR_ROWS + i] if i % period >= 4 or edge[i % period] is None else edge[i % period] for i in range(FR_ROWS)])
+    assert all({0, 1, R_MOD - 1} <= set(col) for col in cols)
+    return cols
+
+
+def fr_check(m, out, want):
+    assert np.array_equal(m.get(out), mont(want))
+
+
+@pytest.mark.parametrize("n", FR_SIZES)
+@pytest.mark.parametrize("mem", [HOST, DEV])
+def test_matrix_fr_vec_op(ctx, fr_rows, mem, n):
+    m, sl = Mem(ctx, mem), slice(1, 1 + n)
+    a, b = fr_rows[0][sl], fr_rows[1][sl]
+    for op, f in ((0, lambda x, y: x + y), (1, lambda x, y: x - y), (2, lambda x, y: x * y)):
+        out = m.out((n, 4))
+        ok(ctx, "czk_fr_vec_op", op=op, a=m.put(mont(a)), b=m.put(mont(b)), out=out, n=n, mem=mem)
+        fr_check(m, out, [f(x, y) for x, y in zip(a, b)])
+
+
+@pytest.mark.parametrize("n", FR_SIZES)
+@pytest.mark.parametrize("mode", ["host", "device", "device_scalar_host"])
+def test_matrix_fr_vec_scale(ctx, fr_rows, mode, n):
+    """the three modes: everything host memory, everything device memory, device vectors with the scalar in host memory"""
+    m = Mem(ctx, HOST if mode == "host" else DEV)
+    mem = {"host": HOST, "device": DEV, "device_scalar_host": DEV | SCALAR_HOST}[mode]
+    a = fr_rows[0][1:1 + n]
+    for k in (0, 1, R_MOD - 1, fr_rows[1][1]):
+        out, kk = m.out((n, 4)), mont([k])
+        ok(ctx, "czk_fr_vec_scale", a=m.put(mont(a)), k=kk if mode == "device_scalar_host" else m.put(kk), out=out, n=n, mem=mem)
+        fr_check(m, out, [x * k for x in a])
+
+
+@pytest.mark.parametrize("n", FR_SIZES)
+@pytest.mark.parametrize("mem", [HOST, DEV])
+def test_matrix_fr_beaver_combine(ctx, fr_rows, mem, n):
+    m = Mem(ctx, mem)
+    x, y, z, sx, oy = (c[1:1 + n] for c in fr_rows)
+    for add_open in (0, 1):
+        out = m.out((n, 4))
+        ok(ctx, "czk_fr_beaver_combine", x=m.put(mont(x)), y=m.put(mont(y)), z=m.put(mont(z)), sx=m.put(mont(sx)), oy=m.put(mont(oy)), add_open=add_open,
+           out=out, n=n, mem=mem)
+        fr_check(m, out, [zz - yy * s - xx * o + add_open * s * o for xx, yy, zz, s, o in zip(x, y, z, sx, oy)])
+
+
+@pytest.mark.parametrize("n", FR_SIZES)
+@pytest.mark.parametrize("mem", [HOST, DEV])
+def test_matrix_fr_repr(ctx, fr_rows, mem, n):
+    """into_repr: Montgomery words -> the residue's own words; from_repr: the way back"""
+    m, a = Mem(ctx, mem), fr_rows[0][1:1 + n]
+    out = m.out((n, 4))
+    ok(ctx, "czk_fr_into_repr", a=m.put(mont(a)), out=out, n=n, mem=mem)
+    assert np.array_equal(m.get(out), ints_to_limbs(a, 4))
+    out = m.out((n, 4))
+    ok(ctx, "czk_fr_from_repr", a=m.put(ints_to_limbs(a, 4)), out=out, n=n, mem=mem)
+    fr_check(m, out, a)
+
+
+@pytest.fixture(scope="module")
+def fr_good(ctx, fr_rows):
+    """per call: arguments of a valid call (three elements; the transforms: two lanes of a 2^3 domain), in host memory where the call takes it and in
+    device memory.  czk_fr_spdz_open's counter is host memory in either case."""
+    def make(m):
+        mem = m.mem
+        vec = lambda lanes=1, n=3: m.put(mont(fr_rows[0][1:1 + lanes * n]))
+        o = lambda lanes=1, n=3: m.out((lanes * n, 4))
+        g = {
+            "czk_fr_vec_op": dict(op=0, a=vec(), b=vec(), out=o(), n=3, mem=mem),
+            "czk_fr_vec_scale": dict(a=vec(), k=vec(1, 1), out=o(), n=3, mem=mem),
+            "czk_fr_beaver_combine": dict(x=vec(), y=vec(), z=vec(), sx=vec(), oy=vec(), add_open=1, out=o(), n=3, mem=mem),
+            "czk_fr_into_repr": dict(a=vec(), out=o(), n=3, mem=mem),
+            "czk_fr_from_repr": dict(a=vec(), out=o(), n=3, mem=mem),
+            "czk_ntt_fr": dict(data=o(2, D), log_d=LOG_D, lanes=2, kind=0, in_len=D, mem=mem),
+        }
+        if mem == DEV:
+            g.update({
+                "czk_fr_spdz_open": dict(shares=vec(4), parties=2, n=3, out_value=o(), out_bad=C.byref(C.c_uint64(77))),
+                "czk_spdz_open_combine": dict(a=vec(2), b=vec(2), tx=vec(2), ty=vec(2), tz=vec(2), parties=1, king_mask=1, sx=o(), oy=o(), chk_a=o(), chk_b=o(),
+                                              ab=o(2), n=3),
+                "czk_ntt_fr_to": dict(src=vec(2, D), src_stride=D, dst=o(2, D), log_d=LOG_D, lanes=2, kind=0, in_len=D, mem=DEV),
+                "czk_witness_map_pre": dict(a=o(2, D), a_len=D, b=o(2, D), b_len=D, log_d=LOG_D, lanes=2),
+                "czk_witness_map_pre_masked": dict(a=o(2, D), a_len=D, b=o(2, D), b_len=D, mask_a=vec(2, D), mask_b=vec(2, D), log_d=LOG_D, lanes=2),
+                "czk_witness_map_post": dict(ab=o(2, D), c=o(2, D), c_len=D, log_d=LOG_D, lanes=2),
+                "czk_witness_map_post_h": dict(ab=o(2, D), c=o(2, D), c_len=D, log_d=LOG_D, lanes=2),
+            })
+        return g
+    return {HOST: make(Mem(ctx, HOST)), DEV: make(Mem(ctx, DEV))}
+
+
+# call -> (the count that makes it empty, the buffers it writes)
+FR_EMPTY = {
+    "czk_fr_vec_op": ("n", "out"), "czk_fr_vec_scale": ("n", "out"), "czk_fr_beaver_combine": ("n", "out"), "czk_fr_into_repr": ("n", "out"),
+    "czk_fr_from_repr": ("n", "out"), "czk_fr_spdz_open": ("n", "out_value"), "czk_spdz_open_combine": ("n", "sx oy chk_a chk_b ab"),
+    "czk_ntt_fr": ("lanes", "data"), "czk_ntt_fr_to": ("lanes", "dst"), "czk_witness_map_pre": ("lanes", "a b"),
+    "czk_witness_map_pre_masked": ("lanes", "a b"), "czk_witness_map_post": ("lanes", "ab c"), "czk_witness_map_post_h": ("lanes", "ab c"),
+}
+FR_HOST_CALLS = ("czk_fr_vec_op", "czk_fr_vec_scale", "czk_fr_beaver_combine", "czk_fr_into_repr", "czk_fr_from_repr", "czk_ntt_fr")
+
+
+@pytest.mark.parametrize("name,mem", [(n, DEV) for n in sorted(FR_EMPTY)] + [(n, HOST) for n in FR_HOST_CALLS])
+def test_empty_fr_call_returns_ok_and_touches_no_output(ctx, fr_good, name, mem):
+    m, (count, outs) = Mem(ctx, mem), FR_EMPTY[name]
+    kw = dict(fr_good[mem][name])
+    kw[count] = 0
+    before = {a: m.get(kw[a]).copy() for a in outs.split()}                  # (still as Mem.out filled them: no call wrote to them)
+    assert all((v.view(np.uint8) == 0xA5).all() for v in before.values())
+    if name == "czk_fr_spdz_open":                                           # the counter is zeroed before the call looks at n
+        bad = C.c_uint64(77)
+        kw["out_bad"] = C.byref(bad)
+    ok(ctx, name, **kw)
+    for a, was in before.items():
+        assert np.array_equal(m.get(kw[a]), was), a
+    if name == "czk_fr_spdz_open":
+        assert bad.value == 0
+
+
+def _each_null(name, args, msg, mem=HOST):
+    return [(name, mem, {a: None}, ERR_ARG, msg) for a in args.split()]
+
+
+# (call, the memory of the valid arguments, the one argument that is wrong, the code, the message)
+FR_ERRORS = _each_null("czk_fr_vec_op", "a b out", "bad vec_op argument") + _each_null("czk_fr_vec_op", "a b out", "bad vec_op argument", DEV)
+FR_ERRORS += [
+    ("czk_fr_vec_op", HOST, {"op": -1}, ERR_ARG, "bad vec_op argument"),
+    ("czk_fr_vec_op", HOST, {"op": 3}, ERR_ARG, "bad vec_op argument"),
+    ("czk_fr_vec_op", HOST, {"op": 3, "n": 0}, ERR_ARG, "bad vec_op argument"),          # a bad op is rejected even by an empty call
+    ("czk_fr_vec_op", HOST, {"op": -1, "n": 0}, ERR_ARG, "bad vec_op argument"),
+    ("czk_fr_vec_op", HOST, {"mem": 2}, ERR_ARG, MEM_MSG),
+    ("czk_fr_vec_scale", HOST, {"k": None}, ERR_ARG, "bad vec_scale argument"),
+    ("czk_fr_vec_scale", HOST, {"k": None, "n": 0}, ERR_ARG, "bad vec_scale argument"),  # ... and a null scalar
+    ("czk_fr_vec_scale", DEV, {"k": None, "n": 0}, ERR_ARG, "bad vec_scale argument"),
+    ("czk_fr_vec_scale", HOST, {"a": None}, ERR_ARG, "bad vec_scale argument"),
+    ("czk_fr_vec_scale", HOST, {"out": None}, ERR_ARG, "bad vec_scale argument"),
+    ("czk_fr_vec_scale", HOST, {"mem": 2}, ERR_ARG, SCALE_MEM_MSG),
+    ("czk_fr_vec_scale", HOST, {"mem": SCALAR_HOST}, ERR_ARG, SCALE_MEM_MSG),             # the scalar flag goes with device vectors only
+    ("czk_fr_vec_scale", HOST, {"mem": 2, "n": 0}, ERR_ARG, SCALE_MEM_MSG),
+]
+FR_ERRORS += _each_null("czk_fr_beaver_combine", "x y z sx oy out", "null beaver argument")
+FR_ERRORS += [("czk_fr_beaver_combine", HOST, {"mem": 2}, ERR_ARG, MEM_MSG)]
+FR_ERRORS += _each_null("czk_fr_spdz_open", "out_bad shares out_value", "bad spdz_open argument", DEV)
+FR_ERRORS += [("czk_fr_spdz_open", DEV, {"parties": 0}, ERR_ARG, "bad spdz_open argument")]
+for _name in ("czk_fr_into_repr", "czk_fr_from_repr"):
+    FR_ERRORS += _each_null(_name, "a out", "null repr argument") + [(_name, HOST, {"mem": 2}, ERR_ARG, MEM_MSG)]
+FR_ERRORS += [("czk_spdz_open_combine", DEV, {"parties": p}, ERR_ARG, "spdz_open_combine: 1 to 32 parties (the king mask has one bit per lane)") for p in (0, 33)]
+FR_ERRORS += _each_null("czk_spdz_open_combine", "a b tx ty tz sx oy chk_a chk_b ab", "null spdz_open_combine argument", DEV)
+FR_ERRORS += [
+    ("czk_ntt_fr", HOST, {"data": None}, ERR_ARG, "null data"),
+    ("czk_ntt_fr", DEV, {"data": None}, ERR_ARG, "null data"),
+    ("czk_ntt_fr", HOST, {"log_d": 48}, ERR_SIZE, ADICITY_MSG),
+    ("czk_ntt_fr", HOST, {"mem": 2}, ERR_ARG, MEM_MSG),
+    ("czk_ntt_fr", HOST, {"kind": -1}, ERR_ARG, "bad ntt kind"),
+    ("czk_ntt_fr", HOST, {"kind": 4}, ERR_ARG, "bad ntt kind"),
+    ("czk_ntt_fr", DEV, {"kind": 4}, ERR_ARG, "bad ntt kind"),
+    ("czk_ntt_fr", HOST, {"in_len": D + 1}, ERR_SIZE, "coeffs.len() > domain size (radix2/mod.rs:100)"),
+    ("czk_ntt_fr", DEV, {"in_len": D + 1}, ERR_SIZE, "coeffs.len() > domain size (radix2/mod.rs:100)"),
+    ("czk_ntt_fr_to", DEV, {"dst": None}, ERR_ARG, "null ntt argument"),
+    ("czk_ntt_fr_to", DEV, {"src": None}, ERR_ARG, "null ntt argument"),
+    ("czk_ntt_fr_to", DEV, {"mem": HOST}, ERR_ARG, "czk_ntt_fr_to takes device memory (host callers copy and use czk_ntt_fr)"),
+    ("czk_ntt_fr_to", DEV, {"log_d": 48}, ERR_SIZE, "domain too large: log2 D exceeds TWO_ADICITY = 47 (radix2/mod.rs:61-63)"),
+    ("czk_ntt_fr_to", DEV, {"src_stride": D - 1}, ERR_ARG, "in_len exceeds the source lane stride"),
+    ("czk_ntt_fr_to", DEV, {"kind": 4}, ERR_ARG, "bad ntt kind"),
+]
+for _name, _ptrs, _lens in (("czk_witness_map_pre", "a b", "a_len b_len"), ("czk_witness_map_pre_masked", "a b mask_a mask_b", "a_len b_len"),
+                            ("czk_witness_map_post", "ab c", "c_len"), ("czk_witness_map_post_h", "ab c", "c_len")):
+    FR_ERRORS += _each_null(_name, _ptrs, WM_NULL_MSG, DEV) + [(_name, DEV, {a: D + 1}, ERR_SIZE, WM_SIZE_MSG) for a in _lens.split()]
+FR_ERRORS += [("czk_witness_map_pre_masked", DEV, {"log_d": 48}, ERR_SIZE, ADICITY_MSG)]
+
+
+@pytest.mark.parametrize("name,mem,wrong,code,msg", FR_ERRORS, ids=[f"{i}-{n[4:]}-{'dev' if m else 'host'}-{'+'.join(w)}" for i, (n, m, w, _, _) in enumerate(FR_ERRORS)])
+def test_one_wrong_fr_argument(ctx, fr_good, name, mem, wrong, code, msg):
+    """the code and the message, every other argument valid; the buffers the call would have written still hold their sentinel"""
+    kw = dict(fr_good[mem][name], **wrong)
+    assert call(ctx, name, **kw) == (code, msg)
+    m = Mem(ctx, mem)
+    for a in FR_EMPTY[name][1].split():
+        if kw[a] is not None:
+            assert (m.get(kw[a]).view(np.uint8) == 0xA5).all(), a
