@@ -18,4 +18,6 @@ from . import keyio  # noqa: F401
 from . import kzg  # noqa: F401
 from . import marlin  # noqa: F401
 from . import plonk  # noqa: F401
+from . import transcript  # noqa: F401
 from . import fri  # noqa: F401
+from .transcript import Transcript  # noqa: F401

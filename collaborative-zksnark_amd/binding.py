@@ -99,6 +99,8 @@ def _load(path):
     L.czk_net_destroy.restype = None
     L.czk_net_stats_reset.restype = None
     L.czk_sha256.restype = None
+    L.czk_blake2s.restype = None
+    L.czk_fs_release.restype = None
     L.czk_groth16_pvk_release.restype = None
     L.czk_fixed_base_release.restype = None
     L.czk_kzg10_vk_release.restype = None
@@ -936,6 +938,15 @@ class Context:
                                          _ptr(out if live else None), C.c_size_t(out_stride), C.c_int(mem)))
         return out
 
+    def fri_fold_at(self, f: int, alpha_dev: int, lanes: int, n: int, stride: int, out: int, out_stride: int):
+        """czk_fr_fri_fold_at: czk_fr_fri_fold on device pointers with alpha read from device memory (one Montgomery Fr at alpha_dev); only enqueues."""
+        self._ck(self._L.czk_fr_fri_fold_at(self._h, _ptr(f), C.c_size_t(lanes), C.c_size_t(n), C.c_size_t(stride), _ptr(alpha_dev), _ptr(out), C.c_size_t(out_stride)))
+
+    def fs_create(self, device: bool = True) -> "Fs":
+        """czk_fs_create on this context: a Fiat-Shamir transcript whose state lives in device memory (every operation a kernel on the context's stream),
+        or, with device=False, in host memory."""
+        return Fs(self, device)
+
     def poly_div_linear(self, coeffs, z, lanes: int = 1, n=None, quotient=None, remainder=None, mem=CZK_MEM_HOST):
         """coeffs / (X - z) per lane; host mode returns (quotient (lanes, n-1, 4), remainder (lanes, 4))."""
         z = np.ascontiguousarray(z, np.uint64).reshape(4)
@@ -1510,6 +1521,106 @@ def sha256(data: bytes, lab: bool = False) -> bytes:
     buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
     (lab_lib() if lab else lib()).czk_sha256(buf, C.c_size_t(len(data)), out)
     return bytes(out)
+
+
+def blake2s(data: bytes) -> bytes:
+    """czk_blake2s (BLAKE2s-256, the hash of the Fiat-Shamir transcripts): for tests against hashlib"""
+    out = (C.c_uint8 * 32)()
+    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+    lib().czk_blake2s(buf, C.c_size_t(len(data)), out)
+    return bytes(out)
+
+
+def fs_keystream(seed32: bytes, word_pos: int, n: int) -> np.ndarray:
+    """czk_fs_keystream: n 32-bit keystream words of the transcripts' generator (rand_chacha's ChaChaRng) under seed32, from word word_pos on"""
+    out = np.zeros(n, dtype=np.uint32)
+    rc = lib().czk_fs_keystream(_key_bytes(seed32, 32), C.c_uint64(word_pos), _ptr(out if n else None), C.c_size_t(n))
+    if rc:
+        raise CzkError(rc, "czk_fs_keystream")
+    return out
+
+
+class Fs:
+    """czk_fs: a Fiat-Shamir transcript (include/czk.h: the reference's FiatShamirRng<Blake2s>).  ctx=None with device=False: a host transcript without a
+    context.  Arrays: numpy (host) or an integer device pointer with the count given; Fr and points are the library's Montgomery arrays."""
+
+    def __init__(self, ctx: "Context | None" = None, device: bool = False):
+        if device and ctx is None:
+            raise ValueError("a device transcript needs a context")
+        self.ctx, self.device = ctx, bool(device)
+        self._L = ctx._L if ctx is not None else lib()
+        self._h = C.c_void_p(0)
+        self._ck(self._L.czk_fs_create(ctx._h if ctx is not None else None, C.c_int(CZK_MEM_DEVICE if device else CZK_MEM_HOST), C.byref(self._h)))
+
+    def _ck(self, rc):
+        if rc:
+            msg = (self._L.czk_last_error(self.ctx._h) or b"").decode() if self.ctx is not None else "czk_fs call on a host transcript"
+            raise CzkError(rc, msg)
+
+    @staticmethod
+    def _mem(x) -> int:
+        return CZK_MEM_HOST if x is None or isinstance(x, np.ndarray) else CZK_MEM_DEVICE
+
+    def put_bytes(self, data, n: int | None = None):
+        """bytes / a uint8 array (host), or a device pointer with n bytes"""
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = np.frombuffer(bytes(data), dtype=np.uint8)
+        if isinstance(data, np.ndarray):
+            data = np.ascontiguousarray(data, np.uint8)
+            n = data.size
+        self._ck(self._L.czk_fs_put_bytes(self._h, _ptr(data if n else None), C.c_size_t(n), C.c_int(self._mem(data))))
+
+    def put_fr(self, v, n: int | None = None):
+        if isinstance(v, np.ndarray):
+            v = np.ascontiguousarray(v, np.uint64)
+            n = v.size // 4
+        self._ck(self._L.czk_fs_put_fr(self._h, _ptr(v if n else None), C.c_size_t(n), C.c_int(self._mem(v))))
+
+    def put_points(self, group: int, pts, inf=None, n: int | None = None):
+        if isinstance(pts, np.ndarray):
+            pts = np.ascontiguousarray(pts, np.uint64)
+            n = pts.size // (12 if group == CZK_G1 else 24)
+            inf = None if inf is None else np.ascontiguousarray(inf, np.uint8).reshape(-1)
+            if inf is not None and inf.size != n:
+                raise ValueError("one infinity flag per point")
+        self._ck(self._L.czk_fs_put_points(self._h, C.c_int(group), _ptr(pts if n else None), _ptr(inf if n else None), C.c_size_t(n), C.c_int(self._mem(pts))))
+
+    def seed(self):
+        self._ck(self._L.czk_fs_seed(self._h))
+
+    def absorb(self):
+        self._ck(self._L.czk_fs_absorb(self._h))
+
+    def squeeze_fr(self, n: int = 1, out: int | None = None):
+        """n Fr::rand draws: a (n, 4) array of Montgomery limbs (blocks, for a device transcript), or written to the device pointer `out` (only enqueued)"""
+        host = np.zeros((n, 4), dtype=np.uint64) if out is None else None
+        self._ck(self._L.czk_fs_squeeze_fr(self._h, _ptr(host if out is None else out), C.c_size_t(n), C.c_int(CZK_MEM_HOST if out is None else CZK_MEM_DEVICE)))
+        return host
+
+    def squeeze_u64(self, n: int = 1, out: int | None = None):
+        host = np.zeros(n, dtype=np.uint64) if out is None else None
+        self._ck(self._L.czk_fs_squeeze_u64(self._h, _ptr(host if out is None else out), C.c_size_t(n), C.c_int(CZK_MEM_HOST if out is None else CZK_MEM_DEVICE)))
+        return host
+
+    def state(self):
+        """czk_fs_state (blocking): (seed, generator position in 32-bit words)"""
+        seed, pos = (C.c_uint8 * 32)(), C.c_uint64(0)
+        self._ck(self._L.czk_fs_state(self._h, seed, C.byref(pos)))
+        return bytes(seed), pos.value
+
+    def release(self):
+        """czk_fs_release.  Release a device transcript BEFORE its context is closed: the call synchronises the context's stream, so once the context is
+        gone it cannot be made, and the handle (a small host struct and about 150 bytes of device memory) is dropped unreleased."""
+        if self._h:
+            if not self.device or self.ctx._h:
+                self._L.czk_fs_release(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class Lanes:

@@ -38,12 +38,12 @@ SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_
            ("msm_bases.hip", ["-DCZK_NOINLINE_MUL"]), ("msm_acc_g1.hip", []),
            ("msm_acc_g2.hip", []), ("msm_red_g2.hip", []), ("msm_heavy_g2.hip", []), ("poly.hip", []), ("share.hip", []), ("share_mul.hip", []), ("gsz_mul.hip", []), ("gsz_dn.hip", []), ("net.hip", ["-DCZK_NOINLINE_MUL"]), ("net_rounds.hip", ["-DCZK_NOINLINE_MUL"]),
            ("pairing.hip", ["-DCZK_NOINLINE_MUL"]), ("fixed_base.hip", []), ("point_codec.hip", ["-DCZK_NOINLINE_MUL"]),
-           ("point_ops.hip", ["-DCZK_NOINLINE_MUL"]), ("group_share.hip", ["-DCZK_NOINLINE_MUL"]), ("pairing_share.hip", ["-DCZK_NOINLINE_MUL"]), ("kzg.hip", ["-DCZK_NOINLINE_MUL"]), ("marlin_index.hip", []), ("plonk_layout.hip", []), ("commit_tree.hip", []), ("merkle.hip", [])]
+           ("point_ops.hip", ["-DCZK_NOINLINE_MUL"]), ("group_share.hip", ["-DCZK_NOINLINE_MUL"]), ("pairing_share.hip", ["-DCZK_NOINLINE_MUL"]), ("kzg.hip", ["-DCZK_NOINLINE_MUL"]), ("marlin_index.hip", []), ("plonk_layout.hip", []), ("commit_tree.hip", []), ("merkle.hip", []), ("fs.hip", ["-DCZK_NOINLINE_MUL"])]
 # lab library only: never compiled into, nor linked with, the product library
 LAB_SOURCES = [(os.path.join("lab", "arith_probe.hip"), []), (os.path.join("lab", "sat_probe.hip"), ["-DCZK_NOINLINE_MUL"]),
                (os.path.join("lab", "msm_sort_probe.hip"), ["-DCZK_NOINLINE_MUL"]), (os.path.join("lab", "msm_bucket_probe.hip"), ["-DCZK_NOINLINE_MUL"]),
                (os.path.join("lab", "merkle_probe.hip"), [])]
-HEADERS = ["field.h", "curve.h", "czk_internal.h", "call.h", "net.h", "sha256.h", "sha256_dev.h", "merkle_hash.h", "merkle_tree_plain.h", "pow_tables.h", "msm_acc.h", "fq2p.h", "fq2pu.h", "fqu.h", "fru.h", "fru_constants.inc", "ntt_pass.h", "te.h", "te_constants.inc", "tower.h", "pairing_steps.h", "pairing_constants.inc",
+HEADERS = ["field.h", "curve.h", "czk_internal.h", "call.h", "net.h", "sha256.h", "sha256_dev.h", "blake2s.h", "chacha20.h", "merkle_hash.h", "merkle_tree_plain.h", "pow_tables.h", "msm_acc.h", "fq2p.h", "fq2pu.h", "fqu.h", "fru.h", "fru_constants.inc", "ntt_pass.h", "te.h", "te_constants.inc", "tower.h", "pairing_steps.h", "pairing_constants.inc",
            os.path.join("..", "..", "include", "czk.h")]
 LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h", "arith_probe.h", "sat_probe.h", "merkle_tree_fused.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

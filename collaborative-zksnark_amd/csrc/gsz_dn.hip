@@ -19,6 +19,7 @@
 // No scratch in any kernel here (profiles/gsz_dn_resource_usage.txt); LDS only for the block reductions.
 #include <cstring>
 
+#include "chacha20.h"
 #include "czk_internal.h"
 #include "pow_tables.h"
 
@@ -37,44 +38,22 @@ struct DnNonce {
     u32 w[3];
 };
 
-__device__ __forceinline__ u32 dn_rotl(u32 x, unsigned n) { return __builtin_rotateleft32(x, n); }
-#define CZK_CHACHA_QR(a, b, c, d)                  \
-    a += b, d ^= a, d = dn_rotl(d, 16);            \
-    c += d, b ^= c, b = dn_rotl(b, 12);            \
-    a += b, d ^= a, d = dn_rotl(d, 8);             \
-    c += d, b ^= c, b = dn_rotl(b, 7)
-
-// The field element of one ChaCha20 block: lo = bytes 0..31, hi = bytes 32..63, little-endian, each mod 2^252; (lo + 2^252 hi) mod r, Montgomery form.
+// The field element of one ChaCha20 block (chacha20.h): lo = bytes 0..31, hi = bytes 32..63, little-endian, each mod 2^252; (lo + 2^252 hi) mod r, Montgomery form.
 // r > 2^252, so both halves are canonical and fp_mul takes them as they are: lo R2 / R = lo R, hi (2^252 R2) / R = 2^252 hi R.
 __device__ __forceinline__ Fr dn_sample(const u32* key, const DnNonce& nonce, u32 counter) {
-    u32 in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7], counter, nonce.w[0], nonce.w[1],
-                  nonce.w[2]};
     u32 x[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = in[i];
-#pragma unroll 1
-    for (int round = 0; round < 10; round++) {
-        CZK_CHACHA_QR(x[0], x[4], x[8], x[12]);
-        CZK_CHACHA_QR(x[1], x[5], x[9], x[13]);
-        CZK_CHACHA_QR(x[2], x[6], x[10], x[14]);
-        CZK_CHACHA_QR(x[3], x[7], x[11], x[15]);
-        CZK_CHACHA_QR(x[0], x[5], x[10], x[15]);
-        CZK_CHACHA_QR(x[1], x[6], x[11], x[12]);
-        CZK_CHACHA_QR(x[2], x[7], x[8], x[13]);
-        CZK_CHACHA_QR(x[3], x[4], x[9], x[14]);
-    }
+    chacha20_block(key, counter, nonce.w[0], nonce.w[1], nonce.w[2], x);
     Fr lo, hi, c_hi;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
-        lo.l[i] = x[i] + in[i];
-        hi.l[i] = x[8 + i] + in[8 + i];
+        lo.l[i] = x[i];
+        hi.l[i] = x[8 + i];
         c_hi.l[i] = FrParams::r2_252(i);
     }
     lo.l[7] &= 0x0fffffffu;
     hi.l[7] &= 0x0fffffffu;
     return fp_add(fp_mul(lo, Fr::r2()), fp_mul(hi, c_hi));
 }
-#undef CZK_CHACHA_QR
 
 __global__ __launch_bounds__(256) void k_fr_random(DnKey key, DnNonce nonce, u32 first, size_t n, u64* out) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)

@@ -103,6 +103,17 @@ __global__ void __launch_bounds__(256) k_fri_fold(const u64* f, size_t stride, s
     }
 }
 
+// the same with alpha read from device memory (one Montgomery Fr): a challenge a device transcript squeezed, never seen by the host
+__global__ void __launch_bounds__(256) k_fri_fold_at(const u64* f, size_t stride, size_t half, size_t lanes, const u64* alpha_at, u64* out, size_t out_stride) {
+    const Fr alpha = fp_load<FrParams>(alpha_at);
+    const size_t total = lanes * half;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t lane = idx / half, j = idx - lane * half;
+        const u64* p = f + 4 * (lane * stride + 2 * j);
+        fp_store<FrParams>(out + 4 * (lane * out_stride + j), fp_add(fp_load<FrParams>(p), fp_mul(alpha, fp_load<FrParams>(p + 4))));
+    }
+}
+
 // n = 2^*log_n, or CZK_ERR_SIZE
 int check_pow2(czk_ctx* ctx, const char* who, size_t n, unsigned* log_n) {
     if (!n || (n & (n - 1))) return set_err(ctx, CZK_ERR_SIZE, std::string(who) + ": n must be a power of two");
@@ -254,4 +265,27 @@ extern "C" int czk_fr_fri_fold(czk_ctx* ctx, const uint64_t* f, size_t lanes, si
     }
     CZK_HIP(ctx, hipGetLastError());
     return so.to_host(out, out_bytes);
+}
+
+extern "C" int czk_fr_fri_fold_at(czk_ctx* ctx, const uint64_t* f, size_t lanes, size_t n, size_t stride, const uint64_t* alpha_dev, uint64_t* out, size_t out_stride) {
+    if (!ctx) return CZK_ERR_ARG;
+    if (n < 2) return set_err(ctx, CZK_ERR_SIZE, "czk_fr_fri_fold_at: n < 2");
+    const size_t half = n / 2;
+    if (stride < n || out_stride < half) return set_err(ctx, CZK_ERR_SIZE, "czk_fr_fri_fold_at: a lane stride is shorter than the lane");
+    if (!lanes) return CZK_OK;
+    size_t f_bytes = 0, out_bytes = 0;
+    CZK_TRY(lane_span_bytes(ctx, "czk_fr_fri_fold_at", lanes, stride, n, &f_bytes));
+    CZK_TRY(lane_span_bytes(ctx, "czk_fr_fri_fold_at", lanes, out_stride, half, &out_bytes));
+    if (!f || !alpha_dev || !out) return set_err(ctx, CZK_ERR_ARG, "czk_fr_fri_fold_at: null argument");
+    if (((uintptr_t)f | (uintptr_t)alpha_dev | (uintptr_t)out) & 15) return set_err(ctx, CZK_ERR_ARG, "czk_fr_fri_fold_at: device pointers to elements are 16-byte aligned");
+    if ((uintptr_t)out < (uintptr_t)f + f_bytes && (uintptr_t)f < (uintptr_t)out + out_bytes) return set_err(ctx, CZK_ERR_ARG, "czk_fr_fri_fold_at: out overlaps f");
+    CZK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t blocks = (lanes * half + 255) / 256, cap = merkle_max_blocks(ctx);
+    {
+        ProfScope ps(ctx, "fri_fold");
+        hipLaunchKernelGGL(k_fri_fold_at, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, ctx->stream, (const u64*)f, stride, half, lanes, (const u64*)alpha_dev,
+                           (u64*)out, out_stride);
+    }
+    CZK_HIP(ctx, hipGetLastError());
+    return CZK_OK;
 }

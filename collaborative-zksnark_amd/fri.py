@@ -5,8 +5,9 @@ Everything is linear in the shares, so a lane is whatever the caller holds: an a
 library's own (czk_lanes): a vector is `Lanes` of (parties, n) elements, a tree `Lanes` of (parties, 2n - 1) 32-byte slots holding digests.
 
 Differences from the reference: any number of parties (the reference's Commitment is a pair); the challenge is a callable `challenge(round, roots) -> int`
-that defaults to polyvm's fixed stand-in -- Fiat-Shamir stays host glue outside this library, and neither the merlin transcript nor the StdRng the reference
-draws from are reproduced --; the query chain runs for any list of start indices, which are arguments; a vector of one element is a tree of one leaf hash
+that defaults to polyvm's fixed stand-in, and neither the merlin transcript nor the StdRng the reference draws from are reproduced: `prove` /
+`verify_proof` below draw the challenges and the query indices from the library's own transcript (transcript.py, the FiatShamirRng<Blake2s> of the
+reference's Marlin and Plonk) instead --; the query chain runs for any list of start indices, which are arguments; a vector of one element is a tree of one leaf hash
 with empty paths.
 """
 from __future__ import annotations
@@ -15,6 +16,7 @@ import numpy as np
 
 from .binding import CZK_FFT, CZK_MEM_DEVICE, CZK_MEM_HOST, Lanes
 from .polyvm import R_MOD, challenge as _fixed_challenge, mont, unmont
+from .transcript import Transcript
 
 _MONT_R_INV = pow(1 << 256, -1, R_MOD)
 TWO_ADICITY = 47
@@ -138,36 +140,72 @@ def commitment_bytes(roots) -> bytes:
 
 
 # ---- client.rs Computation::Fri --------------------------------------------------------------------------------------------------------------
-def commit_phase(ctx, f_lanes, challenge=default_challenge, fold_alpha=None) -> dict:
+def commit_phase(ctx, f_lanes, challenge=default_challenge, fold_alpha=None, transcript=None) -> dict:
     """client.rs:745-777.  f_lanes: `Lanes` (left as it is) or a (lanes, 2^k, 4) array of Montgomery coefficients.  Round i = 0 .. k - 1: the 2^(k - i)
     coefficients, zero-padded to rate 1/2 by the transform's load, are evaluated over the domain of 2^(k - i + 1) points, committed, alpha_i =
     challenge(i, roots_i), and folded.  Evaluations and trees stay on the device.  fold_alpha(i, alpha) -> what to fold with (tests: a dishonest
-    prover).  -> state {"k", "lanes", "rounds": [{"n", "evals", "tree", "roots", "alpha"}], "constant", "coeffs"}; release(state) frees it."""
+    prover).  -> state {"k", "lanes", "rounds": [{"n", "evals", "tree", "roots", "alpha"}], "constant", "coeffs"}; release(state) frees it.
+    transcript: a device `Transcript` in place of the hook (`prove`): a round's roots are absorbed from tree memory, alpha_i is squeezed into device
+    memory and czk_fr_fri_fold_at reads it there, so nothing waits between rounds; one wait at the end brings back the roots, the alphas and the lanes'
+    last element.  Whatever was allocated is freed when a step fails."""
     f = f_lanes if isinstance(f_lanes, Lanes) else upload_lanes(ctx, f_lanes)
     k = f.len.bit_length() - 1
-    if f.len != 1 << k:
-        raise ValueError("the number of coefficients must be a power of two")
     lanes, coeffs, rounds = f.lanes, [f], []
-    for i in range(k):
-        m = 1 << (k - i)
-        evals = ctx.lanes_alloc(lanes, 2 * m)
-        ctx.ntt_fr_to(f.ptr(), f.len, evals.ptr(), k - i + 1, CZK_FFT, lanes=lanes, in_len=m)
-        com = merkle_commit(ctx, evals)
-        alpha = challenge(i, com["roots"]) % R_MOD
-        used = alpha if fold_alpha is None else fold_alpha(i, alpha) % R_MOD
-        nxt = ctx.lanes_alloc(lanes, m // 2)
-        ctx.fri_fold(f.ptr(), mont(used), lanes=lanes, n=m, stride=f.len, out=nxt.ptr(), out_stride=nxt.len, mem=CZK_MEM_DEVICE)
-        rounds.append({"n": 2 * m, "evals": evals, "tree": com["tree"], "roots": com["roots"], "alpha": alpha})
-        coeffs.append(nxt)
-        f = nxt
-    constant = sum(unmont(f.download(lane=ln, n=1)[0]) for ln in range(lanes)) % R_MOD    # `constant.publicize()`: the lanes' sum
-    return {"k": k, "lanes": lanes, "rounds": rounds, "constant": constant, "coeffs": coeffs, "own_input": not isinstance(f_lanes, Lanes)}
+    state = {"k": k, "lanes": lanes, "rounds": rounds, "constant": None, "coeffs": coeffs, "own_input": not isinstance(f_lanes, Lanes)}
+    alphas = None
+    try:
+        if f.len != 1 << k:
+            raise ValueError("the number of coefficients must be a power of two")
+        if transcript is not None and k:
+            alphas = ctx.lanes_alloc(1, k)
+        for i in range(k):
+            m = 1 << (k - i)
+            rd = {"n": 2 * m, "evals": ctx.lanes_alloc(lanes, 2 * m), "tree": None, "roots": None, "alpha": None}
+            rounds.append(rd)
+            ctx.ntt_fr_to(f.ptr(), f.len, rd["evals"].ptr(), k - i + 1, CZK_FFT, lanes=lanes, in_len=m)
+            com = merkle_commit(ctx, rd["evals"], roots=transcript is None)
+            rd["tree"], rd["roots"] = com["tree"], com["roots"]
+            nxt = ctx.lanes_alloc(lanes, m // 2)
+            coeffs.append(nxt)
+            if transcript is None:
+                rd["alpha"] = challenge(i, com["roots"]) % R_MOD
+                used = rd["alpha"] if fold_alpha is None else fold_alpha(i, rd["alpha"]) % R_MOD
+                ctx.fri_fold(f.ptr(), mont(used), lanes=lanes, n=m, stride=f.len, out=nxt.ptr(), out_stride=nxt.len, mem=CZK_MEM_DEVICE)
+            else:
+                for ln in range(lanes):
+                    transcript.put_bytes(rd["tree"].ptr(ln, 4 * m - 2), 32)      # the lane's root, where the tree kernel left it
+                transcript.absorb().squeeze_fr_mont(1, out=alphas.ptr(0, i))
+                ctx.fri_fold_at(f.ptr(), alphas.ptr(0, i), lanes=lanes, n=m, stride=f.len, out=nxt.ptr(), out_stride=nxt.len)
+            f = nxt
+        if transcript is None:
+            last = [f.download(lane=ln, n=1)[0] for ln in range(lanes)]
+        else:
+            h_roots, h_alpha, last = np.zeros((k, lanes, 4), dtype=np.uint64), np.zeros((k, 4), dtype=np.uint64), np.zeros((lanes, 4), dtype=np.uint64)
+            for i, rd in enumerate(rounds):
+                for ln in range(lanes):
+                    rd["tree"].download_deferred(h_roots[i, ln], lane=ln, elem=2 * rd["n"] - 2)
+            if k:
+                alphas.download_deferred(h_alpha)
+            for ln in range(lanes):
+                f.download_deferred(last[ln], lane=ln)
+            ctx.sync()                                                           # the one wait
+            for i, rd in enumerate(rounds):
+                rd["roots"], rd["alpha"] = [h_roots[i, ln].tobytes() for ln in range(lanes)], unmont(h_alpha[i])
+        state["constant"] = sum(unmont(v) for v in last) % R_MOD                 # `constant.publicize()`: the lanes' sum
+    except BaseException:
+        release(state)
+        raise
+    finally:
+        if alphas is not None:
+            alphas.free()
+    return state
 
 
 def release(state: dict):
     for rd in state["rounds"]:
         rd["evals"].free()
-        rd["tree"].free()
+        if rd["tree"] is not None:
+            rd["tree"].free()
     for c in state["coeffs"][0 if state["own_input"] else 1:]:
         c.free()
 
@@ -220,3 +258,50 @@ def verify(ctx, proof: dict, challenge=default_challenge) -> bool:
             if nxt % R_MOD != ((v + vneg) * inv2 + alpha * (v - vneg) % R_MOD * pow(2 * x, -1, R_MOD)) % R_MOD:
                 return False
     return True
+
+
+# ---- non-interactive: challenges and query indices from a Fiat-Shamir transcript ---------------------------------------------------------------
+# The transcript: from_seed(seed); per round absorb(the lanes' roots, 32 bytes each, in lane order) and alpha_i = Fr::rand; after the last round
+# absorb(the constant, as Fr::write) and one u64 per query, taken mod 2^(k + 1), as the start indices.
+def _transcript_tail(t: Transcript, constant: int, k: int, queries: int) -> list:
+    t.put_fr([constant]).absorb()
+    return [x % (1 << (k + 1)) for x in t.squeeze_u64(queries)] if queries else []
+
+
+def prove(ctx, f_lanes, queries: int = 1, seed: bytes = b"fri", device: bool = True) -> dict:
+    """The commit phase with its challenges drawn from a transcript, then query_phase at the indices the transcript gives: query_phase's proof.
+    device=True: the transcript's state lives on the device and commit_phase runs as one enqueued sequence with one wait at its end.  device=False: the
+    same transcript in host memory through commit_phase's challenge hook (one stop per round), for comparison: the proofs are identical."""
+    t = Transcript(ctx, device=True) if device else Transcript()
+    state = None
+    try:
+        t.put_bytes(seed).seed()
+        if device:
+            state = commit_phase(ctx, f_lanes, transcript=t)
+        else:
+            state = commit_phase(ctx, f_lanes, challenge=lambda i, roots: t.put_bytes(b"".join(roots)).absorb().squeeze_fr())
+        starts = _transcript_tail(t, state["constant"], state["k"], queries)
+        t.state()                                   # blocking: raises if a squeeze on the device gave up (the transcript's sticky error word)
+        return query_phase(ctx, state, starts)
+    finally:
+        if state is not None:
+            release(state)
+        t.release()
+
+
+def verify_proof(ctx, proof: dict, seed: bytes = b"fri") -> bool:
+    """`verify` with the alphas and the start indices recomputed by a host transcript from the proof's roots and constant: a proof whose roots, constant
+    or indices were changed draws other challenges and fails."""
+    t = Transcript()
+    t.put_bytes(seed).seed()
+    try:
+        k = proof["k"]
+        if len(proof["roots"]) != k or any(len(r) != proof["lanes"] or any(len(bytes(x)) != 32 for x in r) for r in proof["roots"]):
+            return False
+        alphas = [t.put_bytes(b"".join(bytes(x) for x in roots)).absorb().squeeze_fr() for roots in proof["roots"]]
+        want = _transcript_tail(t, int(proof["constant"]) % R_MOD, k, len(proof["x_indices"]))
+    finally:
+        t.release()
+    if [int(x) for x in proof["x_indices"]] != want:
+        return False
+    return verify(ctx, proof, challenge=lambda i, roots: alphas[i])

@@ -214,7 +214,7 @@ def prover_inputs(B, idx: dict, instance, witness, mask=None, seed: int = 0x3A26
 
 def verifier_key(idx: dict) -> dict:
     """What the verifier keeps of an index: the domain sizes and the twelve index commitments (IndexVerifierKey, marlin/src/data_structures.rs)"""
-    return {"H": idx["H"], "K": idx["K"], "X": idx["X"], "index_cmts": [(np.array(c[0], dtype=np.uint64), np.array(c[1], dtype=np.uint8)) for c in idx["index_cmts"]]}
+    return {"H": idx["H"], "K": idx["K"], "X": idx["X"], "info": dict(idx["info"]), "index_cmts": [(np.array(c[0], dtype=np.uint64), np.array(c[1], dtype=np.uint8)) for c in idx["index_cmts"]]}
 
 
 _INDEX_LABELS = [m + "_" + part for m in "abc" for part in ("row", "col", "val", "row_col")]
@@ -229,9 +229,32 @@ class _Reject(Exception):
     pass
 
 
-def _decide(B, vk, x_ints, out, rng):
+def _decide(B, vk, x_ints, out, rng, fiat_shamir=False):
     H, K, X = vk["H"], vk["K"], vk["X"]
-    alpha, eta_a, eta_b, eta_c, beta, gamma = (challenge("marlin." + t) for t in ("alpha", "eta_a", "eta_b", "eta_c", "beta", "gamma"))
+    x_pad = [int(v) % R_MOD for v in x_ints] + [0] * (X - len(x_ints))
+    if len(x_pad) != X:
+        raise _Reject("public input longer than the input domain")
+    fs = None
+    if fiat_shamir:   # the verifier's own transcript (Marlin::verify, lib.rs:351-408) over the key, the public input and the proof's commitments
+        fs = polyvm.MarlinTranscript(polyvm.marlin_fs_info(vk), vk["index_cmts"], x_pad[1:], H)
+    try:
+        _decide_with(B, vk, x_pad, out, rng, fs)
+    finally:
+        if fs is not None:
+            fs.release()
+
+
+def _decide_with(B, vk, x_pad, out, rng, fs):
+    H, K, X = vk["H"], vk["K"], vk["X"]
+    if fs is None:
+        alpha, eta_a, eta_b, eta_c, beta, gamma = (challenge("marlin." + t) for t in ("alpha", "eta_a", "eta_b", "eta_c", "beta", "gamma"))
+    else:
+        fs.absorb_round(out, polyvm.MARLIN_FS_ROUNDS[0])
+        alpha, eta_a, eta_b, eta_c = fs.draw_outside_domain(), fs.draw(), fs.draw(), fs.draw()
+        fs.absorb_round(out, polyvm.MARLIN_FS_ROUNDS[1])
+        beta = fs.draw_outside_domain()
+        fs.absorb_round(out, polyvm.MARLIN_FS_ROUNDS[2])
+        gamma = fs.draw()
     point = {"beta": beta, "gamma": gamma}
     inv = lambda v: pow(v % R_MOD, -1, R_MOD)   # noqa: E731
     # the published evaluations by (polynomial, point): marlin_prove evaluates what the coefficients need first (mod.rs:155-157, :228-231), then every
@@ -248,9 +271,6 @@ def _decide(B, vk, x_ints, out, rng):
     if next(it["beta"], None) is not None or next(it["gamma"], None) is not None:
         raise _Reject("more evaluations than the query set asks for")
     # the two sumcheck combinations, their coefficients from the challenges, the public input and the evaluations (mod.rs:155-250)
-    x_pad = [int(v) % R_MOD for v in x_ints] + [0] * (X - len(x_ints))
-    if len(x_pad) != X:
-        raise _Reject("public input longer than the input domain")
     wx, x_beta, acc = B.root_of_unity(X), 0, 1
     for xj in x_pad:                                                           # x(beta) = sum_j L_j(beta) x_j over the input domain (:158-163)
         x_beta = (x_beta + vanishing(X, beta) * acc % R_MOD * inv(X * (beta - acc)) % R_MOD * xj) % R_MOD
@@ -280,7 +300,11 @@ def _decide(B, vk, x_ints, out, rng):
     seen = {k: v for k, v in out.items() if k not in ("lcs", "lc_consts")}
     for label, cmt in zip(_INDEX_LABELS, vk["index_cmts"]):
         seen[label + "_cmt"] = cmt
-    ch = challenge("marlin.opening_challenge")
+    if fs is None:
+        ch = challenge("marlin.opening_challenge")
+    else:   # the evaluations the reference absorbs (lib.rs:283-299, the verifier's :392): recomputed here, constants included, never read from the proof
+        fs.absorb_evaluations([(lc_at(label, tag) + consts.get(label, 0)) % R_MOD for label, tag in polyvm.MARLIN_FS_EVALS])
+        ch = fs.opening_challenge()
     for tag in ("beta", "gamma"):
         want, c, terms = 0, 1, []
         for label in _QUERY[tag]:
@@ -302,14 +326,16 @@ def _decide(B, vk, x_ints, out, rng):
         raise _Reject("KZG openings")
 
 
-def verify(B, idx_or_vk: dict, x_ints, out: dict, rng=None) -> bool:
+def verify(B, idx_or_vk: dict, x_ints, out: dict, rng=None, fiat_shamir: bool = False) -> bool:
     """The AHP verifier's decision on a marlin_prove result `out` made on the GpuBackend B with public data lifted onto every lane, for the formatted
     public input x_ints = [1, ...] under the index (or verifier_key) `idx_or_vk`.  The coefficients of both sumcheck combinations are recomputed from the
     challenges, x_ints and the published evaluations -- out["lcs"] / out["lc_consts"] and the prover's "terms" are never read; both combinations must be
     zero, the folded opened values must match, and every KZG opening is checked (kzg.check_openings) with the twelve index commitments taken from the
-    key, not from `out`.  A malformed or rejected proof is False, never an exception."""
+    key, not from `out`.  fiat_shamir=True: the challenges are recomputed by a host transcript (polyvm.MarlinTranscript) from the key, x_ints, the
+    proof's commitments and the evaluations the verifier derives, as a proof made by marlin_prove(..., fiat_shamir=True) needs; out["challenges"] is
+    never read.  A malformed or rejected proof is False, never an exception."""
     try:
-        _decide(B, idx_or_vk, x_ints, out, rng)
+        _decide(B, idx_or_vk, x_ints, out, rng, fiat_shamir)
     except (_Reject, KeyError, IndexError, StopIteration, TypeError, ValueError, AttributeError, czk.CzkError):
         return False
     return True

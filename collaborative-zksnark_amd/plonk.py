@@ -233,11 +233,14 @@ _OPENINGS = {
 }
 
 
-def _decide(B, vk, public, out, rng):
+def _decide(B, vk, public, out, rng, fiat_shamir=False):
     G = int(vk["n_gates"])
     W = 3 * G
     w = B.root_of_unity(W)
-    c = {t: challenge("plonk." + t) for t in ("public.x", "gates.x", "product.r", "wiring.y", "wiring.z", "wiring.x")}
+    if fiat_shamir:   # the verifier's own transcript over the proof's commitments (Verifier, lib.rs:461-572): nothing is read from out["challenges"]
+        c = polyvm.plonk_fs_challenges(out)
+    else:
+        c = {t: challenge("plonk." + t) for t in ("public.x", "gates.x", "product.r", "wiring.y", "wiring.z", "wiring.x")}
     # the verifier's copy of the proof: the index commitments come from the key, and which commitment an opening belongs to and at which point is
     # the verifier's to say, not the proof's
     seen = {k: v for k, v in out.items() if k.endswith("_cmt")}
@@ -287,17 +290,19 @@ def _decide(B, vk, public, out, rng):
         raise _Reject("KZG openings")
 
 
-def verify(B, vk: dict, public: dict, out: dict, rng=None) -> bool:
+def verify(B, vk: dict, public: dict, out: dict, rng=None, fiat_shamir: bool = False) -> bool:
     """Verifier::verify (lib.rs:511-582) on a plonk_prove result `out` made on the GpuBackend B, under the verifier_key `vk` and the public values
     `public` (name -> integer).  The four identities -- public wires, gates, unit product, wiring -- are recomputed from the challenges and the opened
     values; the sixteen KZG openings are checked (kzg.check_openings) on a copy of the proof in which s_cmt and w_cmt are the key's, never the proof's,
     and every opening is tied to the commitment and the point the verifier expects.  The public identity evaluates z(x) = prod (x - x_i) and the
     interpolation v(x) through (x_i, public[name_i]) by Lagrange's formula in host big integers: O(k^2) multiplications and k inversions for k public
-    wires.  ValueError if `public` does not name exactly the key's public wires; a malformed or rejected proof is False, never an exception."""
+    wires.  fiat_shamir=True: the challenges are recomputed by a host transcript from the proof's commitments (polyvm.plonk_fs_challenges), as a
+    proof made by plonk_prove(..., fiat_shamir=True) needs; False: the fixed stand-ins.  A proof of one kind is rejected as the other: its openings
+    are at other points.  ValueError if `public` does not name exactly the key's public wires; a malformed or rejected proof is False, never an exception."""
     if set(public) != set(vk["public_indices"]):
         raise ValueError(f"public values for {sorted(public)}, the key's public wires are {sorted(vk['public_indices'])}")
     try:
-        _decide(B, vk, public, out, rng)
+        _decide(B, vk, public, out, rng, fiat_shamir)
     except (_Reject, KeyError, IndexError, TypeError, ValueError, AttributeError, czk.CzkError):
         return False
     return True

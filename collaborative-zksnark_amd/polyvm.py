@@ -1031,9 +1031,141 @@ def plonk_inputs(B: Backend, n_gates: int, seed: int = 0x9107) -> dict:
     return {"n_gates": n_gates, "p": shared_copy(B, B.random(seed + 1, W)), "s": B.random(seed + 2, n_gates), "w": B.random(seed + 3, W)}
 
 
-def plonk_prove(B: Backend, inp: dict) -> dict:
+# The reference's Plonk transcript (mpc-plonk/src/lib.rs): from_seed(&0u64); every commitment is absorbed where it is made (:397-399, the verifier's
+# recv_commit :485-487) and the challenges are drawn at :283, :316, :207-208, :169, :237 -- in the order the prover runs, which is this list.  No
+# evaluation is absorbed: the reference absorbs none.
+PLONK_FS_SCRIPT = (("absorb", "p"), ("absorb", "pub_q"), ("draw", "public.x"), ("absorb", "gates_q"), ("draw", "gates.x"), ("draw", "wiring.y"),
+                   ("draw", "wiring.z"), ("absorb", "l1"), ("absorb", "t"), ("absorb", "q"), ("draw", "product.r"), ("absorb", "l2_q"), ("draw", "wiring.x"))
+
+
+def fs_put_commitment(t, cm, shifted=None):
+    """ToBytes of a marlin_pc commitment (poly-commit/src/marlin/marlin_pc/data_structures.rs:252-263) onto the Transcript t: comm, the bool
+    `shifted_comm.is_some()`, then the shifted commitment or the empty one (the point at infinity).  cm, shifted: (affine (k, 12) Montgomery limbs,
+    (k,) infinity flags) as GpuBackend settles a commitment -- one row per lane, every lane the same opened commitment; ValueError("not built") for rows
+    that differ (shares nobody opened) or any other shape."""
+    from .binding import CZK_G1
+
+    def one_row(c):
+        try:
+            aff, inf = np.asarray(c[0], dtype=np.uint64).reshape(-1, 12), np.asarray(c[1], dtype=np.uint8).reshape(-1)
+        except (TypeError, ValueError, IndexError, KeyError):
+            raise ValueError("not built") from None
+        if not len(inf) or len(inf) != len(aff) or any(not np.array_equal(aff[i], aff[0]) or inf[i] != inf[0] for i in range(len(inf))):
+            raise ValueError("not built")
+        return aff[:1], inf[:1]
+    empty = (np.zeros((1, 12), dtype=np.uint64), np.ones(1, dtype=np.uint8))
+    t.put_points(CZK_G1, *one_row(cm)).put_bool(shifted is not None).put_points(CZK_G1, *(one_row(shifted) if shifted is not None else empty))
+
+
+# The reference's Marlin transcript (marlin/src/lib.rs:163-300, the verifier's :351-408): the commitments of each prover round in the order the round's
+# oracles are committed (g_1 and g_2 carry their shifted commitment), and the labels whose evaluations are absorbed: every queried combination but
+# LC_WITH_ZERO_EVAL's two (ahp/mod.rs:52), sorted by label (lib.rs:294).
+MARLIN_FS_ROUNDS = (("w", "z_a", "z_b", "mask_poly"), ("t", "g_1", "h_1"), ("g_2", "h_2"))
+MARLIN_FS_EVALS = (("a_denom", "gamma"), ("b_denom", "gamma"), ("c_denom", "gamma"), ("g_1", "beta"), ("g_2", "gamma"), ("t", "beta"), ("z_b", "beta"))
+
+
+def marlin_fs_info(d: dict) -> tuple:
+    """IndexInfo::write's three numbers (ahp/indexer.rs:44-50) of an index or verifier key: num_variables, num_constraints, num_non_zero"""
+    info = d["info"]
+    return int(info["num_variables"]), int(info["num_constraints"]), int(info["num_non_zero"])
+
+
+class MarlinTranscript:
+    """A host Transcript driven as the reference's Marlin drives its fs_rng.  from_seed(to_bytes![b"MARLIN-2019", index_vk, public_input]):
+    IndexVerifierKey::write is index_info as three u64, then the index commitments (data_structures.rs:36-43); public_input is the formatted input
+    without its leading one (unformat_public_input), here as padded to the input domain.  Per round absorb(to_bytes![comms, prover_msg]) with every
+    prover message empty; alpha and beta by sample_element_outside_domain over H (redrawn while the vanishing polynomial is zero), eta_a, eta_b, eta_c
+    and gamma by F::rand; absorb(&evaluations); the opening challenge is u128::rand."""
+
+    def __init__(self, info: tuple, index_cmts, public_input, H: int):
+        from .transcript import Transcript
+        self.t, self.H = Transcript(), H
+        self.t.put_bytes(b"MARLIN-2019").put_u64(*info)
+        for c in index_cmts:
+            fs_put_commitment(self.t, c)
+        self.t.put_fr([int(v) % R_MOD for v in public_input]).seed()
+
+    def absorb_round(self, cmts: dict, labels):
+        """cmts[label + "_cmt"] (and label + "_shifted_cmt" for g_1, g_2), opened"""
+        for label in labels:
+            fs_put_commitment(self.t, cmts[label + "_cmt"], cmts[label + "_shifted_cmt"] if label in ("g_1", "g_2") else None)
+        self.t.absorb()
+
+    def draw(self) -> int:
+        return self.t.squeeze_fr()
+
+    def draw_outside_domain(self) -> int:
+        v = self.draw()
+        while vanishing(self.H, v) == 0:                                           # (bounded: 2^-200 per turn)
+            v = self.draw()
+        return v
+
+    def absorb_evaluations(self, values):
+        self.t.put_fr([int(v) % R_MOD for v in values]).absorb()
+
+    def opening_challenge(self) -> int:
+        return self.t.squeeze_u128()
+
+    def release(self):
+        self.t.release()
+
+
+class PlonkTranscript:
+    """A host Transcript driven as the reference's Plonk drives its fs_rng.  A commitment is absorbed as to_bytes![c] of the labelled marlin_pc
+    commitment (poly-commit/src/marlin/marlin_pc/data_structures.rs:252-263): comm, the bool `shifted_comm.is_some()`, then the shifted commitment or
+    the empty one (the point at infinity).  No commitment here has a degree bound (the bound on p is not built: DESIGN 7f), so the bool is false."""
+
+    def __init__(self):
+        from .transcript import Transcript
+        self.t = Transcript()
+        self.t.put_u64(0).seed()                                                   # FiatShamirRng::from_seed(&0u64)
+
+    def absorb_commitment(self, cm):
+        """cm: (affine (k, 12) Montgomery limbs, (k,) infinity flags) as GpuBackend settles a commitment -- one row per lane, every lane the same opened
+        commitment; ValueError("not built") for anything else"""
+        fs_put_commitment(self.t, cm)
+        self.t.absorb()
+
+    def draw(self) -> int:
+        return self.t.squeeze_fr()
+
+    def release(self):
+        self.t.release()
+
+
+def plonk_fs_challenges(cmts: dict) -> dict:
+    """The verifier's replay: the challenges of PLONK_FS_SCRIPT over the commitments cmts[label + "_cmt"], keyed by the stand-in tags without "plonk." """
+    fs, c = PlonkTranscript(), {}
+    try:
+        for what, name in PLONK_FS_SCRIPT:
+            if what == "absorb":
+                fs.absorb_commitment(cmts[name + "_cmt"])
+            else:
+                c[name] = fs.draw()
+    finally:
+        fs.release()
+    return c
+
+
+def plonk_prove(B: Backend, inp: dict, fiat_shamir: bool = False) -> dict:
     """Local compute of `Prover::prove` (mpc-plonk/src/lib.rs:430-448) on plonk_inputs, or on plonk.prover_inputs for a circuit of the caller's
-    (then with inp["public_points"], any number of public wires).  Returns every commitment and opening in the reference's order."""
+    (then with inp["public_points"], any number of public wires).  Returns every commitment and opening in the reference's order.
+    fiat_shamir=False: the challenges are polyvm.challenge's fixed stand-ins, every output what it always was.  fiat_shamir=True: they come from a
+    PlonkTranscript that absorbs each commitment at the transcript point that settles it, and the result gains "challenges", keyed by the stand-in
+    tags.  On a backend with `sharing` in lanes form (additive, SPDZ or GSZ) each commitment is opened at the transcript point where it is absorbed
+    -- the reference's `c.commitment.publicize()` (lib.rs:396), through open_shared_proof's opening with its MAC or degree checks (SharingError when one
+    fails) -- and the result stays on share lanes as ever.  Sharing(rank=...), where opening is an exchange between processes: ValueError("not built")."""
+    if fiat_shamir and getattr(B, "sharing", None) is not None and B.sharing.rank is not None:
+        raise ValueError("not built")
+    fs = PlonkTranscript() if fiat_shamir else None
+    try:
+        return _plonk_prove(B, inp, fs)
+    finally:
+        if fs is not None:
+            fs.release()
+
+
+def _plonk_prove(B: Backend, inp: dict, fs) -> dict:
     G = inp["n_gates"]
     W = 3 * G
     w = B.root_of_unity(W)                                                     # domains.wires.group_gen (mixed radix)
@@ -1041,8 +1173,23 @@ def plonk_prove(B: Backend, inp: dict) -> dict:
     out = {}
     p, s_pub, w_pub = inp["p"], inp["s"], inp["w"]
 
+    chal = {}
+
     def commit(label, a):
         out[label + "_cmt"] = B.commit(a)
+
+    def settle(*labels):
+        """the transcript point after the commitments `labels`: they settle, and are absorbed in that order"""
+        B.transcript_point()
+        for label in (labels if fs is not None else ()):
+            cm = resolved(out[label + "_cmt"])
+            if getattr(B, "sharing", None) is not None:
+                cm = open_shared_proof(B, {label + "_cmt": cm})[label + "_cmt"]          # `c.commitment.publicize()`
+            fs.absorb_commitment(cm)
+
+    def draw(tag):
+        chal[tag] = challenge(tag) if fs is None else fs.draw()
+        return chal[tag]
 
     def open_(label, a, x, of=None):
         out[label] = B.open_at(a, x, public=of is None)
@@ -1059,8 +1206,8 @@ def plonk_prove(B: Backend, inp: dict) -> dict:
     for x_pub in inp.get("public_points", [w]):
         q_pub = B.quotient(q_pub, x_pub)
     commit("pub_q", q_pub)
-    B.transcript_point()
-    x = challenge("plonk.public.x")
+    settle("p", "pub_q")
+    x = draw("plonk.public.x")
     open_("pub_q_open", q_pub, x, "pub_q")
     open_("pub_p_open", p, x, "p")
     # prove_gates (:295-340): d = s (p + pw) + (1 - s)(p pw) - pww, q = d / v_gates
@@ -1070,16 +1217,16 @@ def plonk_prove(B: Backend, inp: dict) -> dict:
     d = B.sub(_padded_add(B, B.poly_mul(s_pub, B.add(p, pw)), B.poly_mul(one_minus_s, B.poly_mul(p, pw))), B.resized(pww, G + 2 * W - 2))
     q_gates, _r = B.div_vanishing(d, G)
     commit("gates_q", q_gates)
-    B.transcript_point()
-    x = challenge("plonk.gates.x")
+    settle("gates_q")
+    x = draw("plonk.gates.x")
     open_("gates_s_open", s_pub, x)
     open_("gates_p_open", p, x, "p")
     open_("gates_q_open", q_gates, x, "gates_q")
     open_("gates_p_w_open", p, w * x % R_MOD, "p")
     open_("gates_p_w2_open", p, w * w % R_MOD * x % R_MOD, "p")
     # prove_wiring (:201-257) over the wire domain
-    B.transcript_point()
-    y, z = challenge("plonk.wiring.y"), challenge("plonk.wiring.z")
+    settle()
+    y, z = draw("plonk.wiring.y"), draw("plonk.wiring.z")
     p_evals = B.ntt(p, W, FFT)
     w_evals = B.ntt(w_pub, W, FFT)
     yx_z = B.ntt(B.upload(np.stack([mont(z), mont(y)])), W, FFT)
@@ -1096,8 +1243,8 @@ def plonk_prove(B: Backend, inp: dict) -> dict:
     tw_c = B.ntt(B.shift(t, w), W, COSET_FFT)
     q_up = B.ntt(B.scale(B.sub(tw_c, B.mul(f_c, t_c)), zinv_w), W, COSET_IFFT)
     commit("q", q_up)
-    B.transcript_point()
-    r = challenge("plonk.product.r")
+    settle("l1", "t", "q")
+    r = draw("plonk.product.r")
     open_("t_wr_open", t, w * r % R_MOD, "t")
     open_("t_r_open", t, r, "t")
     open_("t_wk_open", t, pow(w, W - 1, R_MOD), "t")
@@ -1110,13 +1257,15 @@ def plonk_prove(B: Backend, inp: dict) -> dict:
     den_v = B.ntt(den_c, W, COSET_FFT)
     l2_q = B.ntt(B.scale(B.sub(B.mul(l1_v, den_v), num_v), zinv_w), W, COSET_IFFT)
     commit("l2_q", l2_q)
-    B.transcript_point()
-    x = challenge("plonk.wiring.x")
+    settle("l2_q")
+    x = draw("plonk.wiring.x")
     open_("l2_q_x_open", l2_q, x, "l2_q")
     open_("w_x_open", w_pub, x)
     open_("l1_x_open", l1, x, "l1")
     open_("p_x_open", p, x, "p")
     B.transcript_point()
+    if fs is not None:
+        out["challenges"] = dict(chal)
     return resolved(out)
 
 
@@ -1166,12 +1315,46 @@ def marlin_inputs(B: Backend, n_constraints: int, seed: int = 0x3A21) -> dict:
     return inp
 
 
-def marlin_prove(B: Backend, inp: dict) -> dict:
+def marlin_prove(B: Backend, inp: dict, fiat_shamir: bool = False) -> dict:
     """Local compute of the three AHP prover rounds (marlin/src/ahp/prover.rs:300-704) and of Marlin::prove's commitments and
     openings (marlin/src/lib.rs:176-318) on marlin_inputs.  Witness-side polynomials are share lanes, the arithmetised matrices
-    and everything in the third round are public, as in the reference."""
+    and everything in the third round are public, as in the reference.
+    fiat_shamir=False: the challenges are polyvm.challenge's fixed stand-ins, every output what it always was.  fiat_shamir=True (inputs of
+    marlin.index / marlin.prover_inputs only: the transcript needs the index's numbers and the public input): alpha, eta_a, eta_b, eta_c, beta, gamma
+    and the opening challenge come from a MarlinTranscript, and the result gains "challenges", keyed by the stand-in tags; the blinding stand-ins
+    ("marlin.blind.*") stand for zk_rng and stay.  On a backend with `sharing` in lanes form each round's commitments and the absorbed evaluations are
+    opened where the transcript takes them, as open_shared_proof opens them; Sharing(rank=...): ValueError("not built")."""
+    fs = None
+    if fiat_shamir:
+        if getattr(B, "sharing", None) is not None and B.sharing.rank is not None:
+            raise ValueError("not built")
+        if not inp.get("real_lcs") or "x_ints" not in inp or "info" not in inp:
+            raise ValueError("fiat_shamir=True needs a real index and assignment (marlin.index, marlin.prover_inputs)")
+        fs = MarlinTranscript(marlin_fs_info(inp), inp["index_cmts"], inp["x_ints"][1:], inp["H"])
+    try:
+        return _marlin_prove(B, inp, fs)
+    finally:
+        if fs is not None:
+            fs.release()
+
+
+def _marlin_prove(B: Backend, inp: dict, fs) -> dict:
     H, K, X, b_size = inp["H"], inp["K"], inp["X"], inp["b_size"]
     out = {}
+    chal = {}
+    shared = getattr(B, "sharing", None) is not None
+
+    def settle(rnd=None):
+        """a transcript point; with a transcript, round `rnd`'s commitments are opened (on shares) and absorbed"""
+        B.transcript_point()
+        if fs is not None and rnd is not None:
+            keys = [l + sfx for l in MARLIN_FS_ROUNDS[rnd] for sfx in (("_cmt", "_shifted_cmt") if l in ("g_1", "g_2") else ("_cmt",))]
+            cm = {k: resolved(out[k]) for k in keys}
+            fs.absorb_round(open_shared_proof(B, cm) if shared else cm, MARLIN_FS_ROUNDS[rnd])
+
+    def draw(tag, outside=False):
+        chal[tag] = challenge(tag) if fs is None else (fs.draw_outside_domain() if outside else fs.draw())
+        return chal[tag]
     blind = {}      # label -> blinding polynomial of a hiding commitment (share lanes, three coefficients)
 
     def commit(label, a, hiding=False):
@@ -1203,8 +1386,9 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
     for label, a in (("w", w_poly), ("z_a", z_a), ("z_b", z_b), ("mask_poly", mask_poly)):
         commit(label, a, hiding=label != "mask_poly")                             # hiding bounds Some(1), Some(1), Some(1), None (:386-390)
     # ---- second round (:439-556) ----------------------------------------------------------------------------
-    B.transcript_point()
-    alpha, eta_a, eta_b, eta_c = (challenge("marlin." + t) for t in ("alpha", "eta_a", "eta_b", "eta_c"))
+    settle(0)
+    alpha = draw("marlin.alpha", outside=True)
+    eta_a, eta_b, eta_c = (draw("marlin." + t) for t in ("eta_a", "eta_b", "eta_c"))
     z_c = B.poly_mul(z_a, z_b)                                                    # shared x shared (:466)
     summed = _padded_add(B, B.scale(z_c, eta_c), B.add(B.scale(z_a, eta_a), B.scale(z_b, eta_b)))   # (:468-476)
     # r(alpha, X) on H, unnormalised bivariate Lagrange: (alpha^|H| - 1) / (alpha - h^i)  (:480-482), public
@@ -1238,8 +1422,8 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
             # (`shifted_rand`, marlin_pc/mod.rs:218-232)
             commit("g_1_shifted", a, hiding=True)
     # ---- third round (:585-704): everything public ---------------------------------------------------------------
-    B.transcript_point()
-    beta = challenge("marlin.beta")
+    settle(1)
+    beta = draw("marlin.beta", outside=True)
     vh = vanishing(H, alpha) * vanishing(H, beta) % R_MOD
     etas = {"a": eta_a, "b": eta_b, "c": eta_c}
     f_evals, den_b, val_b = None, {}, {}
@@ -1269,8 +1453,8 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
         if label == "g_2":
             commit("g_2_shifted", a)                                                # degree bound |K| - 2
     # ---- evaluations and openings (marlin/src/lib.rs:262-318) ---------------------------------------------------------------
-    B.transcript_point()
-    gamma = challenge("marlin.gamma")
+    settle(2)
+    gamma = draw("marlin.gamma")
     idx = inp["index_polys"]                                                       # row, col, val, row_col of A, B, C
     row, col, val, row_col = ({m: idx[4 * i + j] for i, m in enumerate("abc")} for j in range(4))
     polys = {"w": w_poly, "z_a": z_a, "z_b": z_b, "mask_poly": mask_poly, "t": t_poly, "g_1": g_1, "h_1": h_1, "g_2": g_2, "h_2": h_2}
@@ -1289,11 +1473,14 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
     point = {"beta": beta, "gamma": gamma}
     query = {"beta": ["g_1", "outer_sumcheck", "t", "z_b"], "gamma": ["a_denom", "b_denom", "c_denom", "g_2", "inner_sumcheck"]}   # verifier_query_set (ahp/verifier.rs:143-146, 207-211), labels in BTreeSet order
 
+    eval_of = {}                                                                   # (polynomial, point tag) -> its first place in out["evals_" + tag]
+
     def lc_eval(label, tag):
         """EvaluationsProvider::get_lc_eval for the prover's polynomials (ahp/mod.rs:288-312): every polynomial of the combination
         is evaluated at the point (Polynomial::evaluate), the sum is publicized"""
         for _, name in lcs[label]:
             out.setdefault("evals_" + tag, []).append(B.evaluate(polys[name], point[tag]))
+            eval_of.setdefault((name, tag), len(out["evals_" + tag]) - 1)
     # construct_linear_combinations evaluates what the coefficients of the two sumcheck combinations need (:155-157, :228-231) ...
     for label, tag in (("z_b", "beta"), ("t", "beta"), ("g_1", "beta"), ("a_denom", "gamma"), ("b_denom", "gamma"), ("c_denom", "gamma"), ("g_2", "gamma")):
         lc_eval(label, tag)
@@ -1342,7 +1529,11 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
             consts[m + "_denom"] = beta * alpha % R_MOD
         out["lc_consts"] = consts
         out["lcs"] = {k: list(v) for k, v in lcs.items()}
-    ch = challenge("marlin.opening_challenge")
+        if fs is not None:
+            # `evaluations` (lib.rs:283-299): get_lc_eval of every queried combination but the two sumchecks, constants included, sorted by label, publicized
+            fs.absorb_evaluations([(sum(cf * val(out["evals_" + tag][eval_of[(name, tag)]]) for cf, name in lcs[label]) + consts.get(label, 0)) % R_MOD
+                                   for label, tag in MARLIN_FS_EVALS])
+    ch = draw("marlin.opening_challenge") if fs is None else chal.setdefault("marlin.opening_challenge", fs.opening_challenge())
     # PC::open_combinations (poly-commit/src/marlin/mod.rs:213-300): one polynomial per combination ...
     lc_poly = {}
     for label, terms in lcs.items():
@@ -1397,6 +1588,8 @@ def marlin_prove(B: Backend, inp: dict) -> dict:
             so["proof"] = CommitmentSum(B, so["proof"], B.commit(sh_rand.pop("_wit"), key="gamma"))
         out["open_" + tag + "_shifted"] = so
     B.transcript_point()
+    if fs is not None:
+        out["challenges"] = dict(chal)
     return resolved(out)
 
 

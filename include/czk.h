@@ -773,6 +773,44 @@ int czk_fr_merkle_verify(czk_ctx* ctx, const uint8_t* roots, size_t lanes, size_
                          const uint8_t* paths, const uint64_t* values, uint8_t* ok, size_t* out_bad, int mem);
 int czk_fr_fri_fold(czk_ctx* ctx, const uint64_t* f, size_t lanes, size_t n, size_t stride, const uint64_t* alpha, uint64_t* out, size_t out_stride,
                     int mem);
+/* czk_fr_fri_fold on DEVICE arrays with alpha_dev a pointer to one Montgomery Fr in DEVICE memory (16-byte aligned), read by the kernel: a challenge that
+ * czk_fs_squeeze_fr wrote there and the host never saw.  Only enqueues.  Same rules and the same values as czk_fr_fri_fold with CZK_MEM_DEVICE. */
+int czk_fr_fri_fold_at(czk_ctx* ctx, const uint64_t* f, size_t lanes, size_t n, size_t stride, const uint64_t* alpha_dev, uint64_t* out, size_t out_stride);
+
+/* ---- Fiat-Shamir transcripts: the reference's FiatShamirRng<Blake2s> (marlin/src/rng.rs, mpc-plonk/src/util.rs:44-108), fs.hip -----------------------------
+ * State: a 32-byte seed and rand_chacha 0.2's ChaChaRng keyed with it (ChaCha20, 64-bit block counter, stream id 0).  from_seed(m): seed = Blake2s(m);
+ * absorb(m): seed = Blake2s(m || seed); both reseed the generator and reset its position, counted in 32-bit keystream words.  A message is PUT piece by
+ * piece (it streams into the hash) and closed by czk_fs_seed (as from_seed) or czk_fs_absorb (as absorb); an empty message is allowed.
+ * ToBytes of what is put: bytes as they are; Fr (Montgomery limbs, as everywhere in this header) as into_repr() in 32 little-endian bytes; an affine point
+ * (czk_msm's layout, flags in `inf` or NULL = none infinite) as x || y || infinity byte, Fq = 48 bytes, Fq2 = c0 then c1: 97 bytes for G1, 193 for G2; a
+ * flagged point is written as the reference's zero(), x = 0 and y = 1.  No length prefixes (algebra/ff/src/bytes.rs: Vec and slices write their items).
+ * Draws: u64 = two keystream words, low first (a u128 is two u64, low first); Fr::rand = four u64 into the limbs low first, the top limb masked with
+ * u64::MAX >> 3, the limbs taken AS the Montgomery representation, redrawn until < r.  Fr results are Montgomery limbs.
+ * mem at creation: CZK_MEM_HOST = the state lives in host memory, plain C++, ctx may be NULL (a verifier without a GPU); CZK_MEM_DEVICE = the state lives in
+ * device memory and every operation is a kernel of one workgroup on the context's stream.  The `mem` of a put or a squeeze says where THAT array lives:
+ *   host transcript: CZK_MEM_HOST only (a DEVICE array with work to do: CZK_ERR_ARG).
+ *   device transcript, put: HOST data is copied in stream order (the buffer is free on return), DEVICE data is read by the kernel; both only enqueue.
+ *     Byte pointers need 1-byte alignment, Fr and point pointers 8-byte.
+ *   device transcript, squeeze: DEVICE only enqueues, HOST blocks for the read-back.
+ * A squeeze before the first czk_fs_seed, or while the pending message is not empty: CZK_ERR_ARG.  n = 0 / len = 0: CZK_OK, nothing changes.
+ * A squeeze_fr gives up after 256 rejected draws of one element (probability 0.42^256), writes zero and sets the state's sticky error word: no device loop
+ * is unbounded.  czk_fs_state and every blocking call of a transcript whose word is set return CZK_ERR_CHECK.
+ * czk_fs_state: blocking; seed32 (32 bytes) and word_pos in HOST memory, either may be NULL.  For tests and for comparing the two forms.
+ * czk_blake2s: BLAKE2s-256 (RFC 7693, no key) of `len` host bytes; czk_fs_keystream: n keystream words of the generator under seed32 from word word_pos on
+ * (out[i] = word word_pos + i).  Both are host code and need no context. */
+typedef struct czk_fs czk_fs;
+void czk_blake2s(const void* data, size_t len, uint8_t* out32);
+int czk_fs_keystream(const uint8_t* seed32, uint64_t word_pos, uint32_t* out, size_t n);
+int czk_fs_create(czk_ctx* ctx, int mem, czk_fs** out);
+void czk_fs_release(czk_fs* fs);
+int czk_fs_put_bytes(czk_fs* fs, const void* p, size_t len, int mem);
+int czk_fs_put_fr(czk_fs* fs, const uint64_t* v, size_t n, int mem);
+int czk_fs_put_points(czk_fs* fs, int group, const uint64_t* pts, const uint8_t* inf, size_t n, int mem);
+int czk_fs_seed(czk_fs* fs);
+int czk_fs_absorb(czk_fs* fs);
+int czk_fs_squeeze_fr(czk_fs* fs, uint64_t* out, size_t n, int mem);
+int czk_fs_squeeze_u64(czk_fs* fs, uint64_t* out, size_t n, int mem);
+int czk_fs_state(czk_fs* fs, uint8_t* seed32, uint64_t* word_pos);
 
 /* DensePolynomial / (X - z): KZG10::compute_witness_polynomial (poly-commit/src/kzg10/mod.rs:200-224; shares divide
  * lane-wise because the divisor is public, mpc-algebra/src/share/add.rs:148-156).  coeffs: lanes x n Fr, low degree

@@ -900,6 +900,66 @@ struct MerkleTree {
 inline void fri_fold(const Context& ctx, const uint64_t* f, size_t lanes, size_t n, size_t stride, const Fr& alpha, uint64_t* out, size_t out_stride, int mem) {
     ctx.check(czk_fr_fri_fold(ctx.raw(), f, lanes, n, stride, alpha.l, out, out_stride, mem));
 }
+// the same on DEVICE arrays with alpha read from device memory (one Montgomery Fr a device transcript squeezed there); only enqueues
+inline void fri_fold_at(const Context& ctx, const uint64_t* f, size_t lanes, size_t n, size_t stride, const uint64_t* alpha_dev, uint64_t* out, size_t out_stride) {
+    ctx.check(czk_fr_fri_fold_at(ctx.raw(), f, lanes, n, stride, alpha_dev, out, out_stride));
+}
+
+// marlin/src/rng.rs FiatShamirRng<Blake2s> (mpc-plonk/src/util.rs:44-108 is the same construction) over czk_fs: seed = Blake2s(message), absorb: seed =
+// Blake2s(message || seed), draws from rand_chacha's ChaChaRng keyed with the seed.  The reference builds each message with to_bytes![..]; here it is put
+// piece by piece -- bytes as they are, Fr and affine points (Montgomery limbs) as their ToBytes -- and closed by from_seed() / absorb().
+//   FiatShamirRng()     state in host memory: no context, no GPU (a verifier)
+//   FiatShamirRng(ctx)  state in device memory: every call is a kernel on the context's stream; data and results may be DEVICE pointers (mem)
+class FiatShamirRng {
+  public:
+    FiatShamirRng() { check(czk_fs_create(nullptr, CZK_MEM_HOST, &fs_)); }
+    explicit FiatShamirRng(const Context& ctx) : ctx_(&ctx) { check(czk_fs_create(ctx.raw(), CZK_MEM_DEVICE, &fs_)); }
+    ~FiatShamirRng() { czk_fs_release(fs_); }
+    FiatShamirRng(const FiatShamirRng&) = delete;
+    FiatShamirRng& operator=(const FiatShamirRng&) = delete;
+    czk_fs* raw() const { return fs_; }
+    FiatShamirRng& put_bytes(const void* p, size_t len, int mem = CZK_MEM_HOST) { return check(czk_fs_put_bytes(fs_, p, len, mem)); }
+    FiatShamirRng& put_u64(uint64_t v) {   // u64::write: little-endian
+        uint8_t b[8];
+        for (int i = 0; i < 8; i++) b[i] = (uint8_t)(v >> (8 * i));
+        return put_bytes(b, 8);
+    }
+    FiatShamirRng& put_fr(const uint64_t* v, size_t n, int mem = CZK_MEM_HOST) { return check(czk_fs_put_fr(fs_, v, n, mem)); }
+    FiatShamirRng& put_fr(const std::vector<Fr>& v) { return put_fr(v.empty() ? nullptr : v[0].l, v.size()); }
+    FiatShamirRng& put_points(int group, const uint64_t* pts, const uint8_t* inf, size_t n, int mem = CZK_MEM_HOST) {
+        return check(czk_fs_put_points(fs_, group, pts, inf, n, mem));
+    }
+    FiatShamirRng& from_seed() { return check(czk_fs_seed(fs_)); }
+    FiatShamirRng& absorb() { return check(czk_fs_absorb(fs_)); }
+    Fr rand_fr() {   // Fr::rand(&mut fs_rng); blocks for a device transcript
+        Fr r;
+        check(czk_fs_squeeze_fr(fs_, r.l, 1, CZK_MEM_HOST));
+        return r;
+    }
+    uint64_t next_u64() {
+        uint64_t r = 0;
+        check(czk_fs_squeeze_u64(fs_, &r, 1, CZK_MEM_HOST));
+        return r;
+    }
+    void rand_u128(uint64_t out[2]) { check(czk_fs_squeeze_u64(fs_, out, 2, CZK_MEM_HOST)); }   // u128::rand: low half first
+    // n draws into `out` (`mem`); for a device transcript CZK_MEM_DEVICE only enqueues
+    void squeeze_fr(uint64_t* out, size_t n, int mem) { check(czk_fs_squeeze_fr(fs_, out, n, mem)); }
+    void squeeze_u64(uint64_t* out, size_t n, int mem) { check(czk_fs_squeeze_u64(fs_, out, n, mem)); }
+    // (seed, generator position in 32-bit keystream words); blocking
+    uint64_t state(uint8_t seed32[32]) {
+        uint64_t pos = 0;
+        check(czk_fs_state(fs_, seed32, &pos));
+        return pos;
+    }
+
+  private:
+    FiatShamirRng& check(int rc) {
+        if (rc != CZK_OK) throw Panic(rc, ctx_ ? czk_last_error(ctx_->raw()) : "czk_fs call on a host transcript failed");
+        return *this;
+    }
+    const Context* ctx_ = nullptr;
+    czk_fs* fs_ = nullptr;
+};
 
 // mpc-snarks/src/groth/r1cs_to_qap.rs:47-113 -- the NTT / pointwise sequence of witness_map for a single prover
 // (T = Fr).  `a`, `b`, `c` are the evaluated constraint rows (a[0..N), then the instance copy; :67-83, :95-100).

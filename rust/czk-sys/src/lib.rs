@@ -24,6 +24,10 @@ pub struct czk_r1cs_matrix {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct czk_fs {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct czk_fixed_base {
     _private: [u8; 0],
 }
@@ -196,6 +200,19 @@ extern "C" {
     pub fn czk_fr_merkle_open(ctx: *mut czk_ctx, a: *const u64, lanes: usize, n: usize, stride: usize, tree: *const u8, tree_stride: usize, idx: *const u64, q: usize, out_shares: *mut u64, out_paths: *mut u8, mem: c_int) -> c_int;
     pub fn czk_fr_merkle_verify(ctx: *mut czk_ctx, roots: *const u8, lanes: usize, n: usize, idx: *const u64, q: usize, shares: *const u64, paths: *const u8, values: *const u64, ok: *mut u8, out_bad: *mut usize, mem: c_int) -> c_int;
     pub fn czk_fr_fri_fold(ctx: *mut czk_ctx, f: *const u64, lanes: usize, n: usize, stride: usize, alpha: *const u64, out: *mut u64, out_stride: usize, mem: c_int) -> c_int;
+    pub fn czk_fr_fri_fold_at(ctx: *mut czk_ctx, f: *const u64, lanes: usize, n: usize, stride: usize, alpha_dev: *const u64, out: *mut u64, out_stride: usize) -> c_int;
+    pub fn czk_blake2s(data: *const c_void, len: usize, out32: *mut u8);
+    pub fn czk_fs_keystream(seed32: *const u8, word_pos: u64, out: *mut u32, n: usize) -> c_int;
+    pub fn czk_fs_create(ctx: *mut czk_ctx, mem: c_int, out: *mut *mut czk_fs) -> c_int;
+    pub fn czk_fs_release(fs: *mut czk_fs);
+    pub fn czk_fs_put_bytes(fs: *mut czk_fs, p: *const c_void, len: usize, mem: c_int) -> c_int;
+    pub fn czk_fs_put_fr(fs: *mut czk_fs, v: *const u64, n: usize, mem: c_int) -> c_int;
+    pub fn czk_fs_put_points(fs: *mut czk_fs, group: c_int, pts: *const u64, inf: *const u8, n: usize, mem: c_int) -> c_int;
+    pub fn czk_fs_seed(fs: *mut czk_fs) -> c_int;
+    pub fn czk_fs_absorb(fs: *mut czk_fs) -> c_int;
+    pub fn czk_fs_squeeze_fr(fs: *mut czk_fs, out: *mut u64, n: usize, mem: c_int) -> c_int;
+    pub fn czk_fs_squeeze_u64(fs: *mut czk_fs, out: *mut u64, n: usize, mem: c_int) -> c_int;
+    pub fn czk_fs_state(fs: *mut czk_fs, seed32: *mut u8, word_pos: *mut u64) -> c_int;
     pub fn czk_poly_div_linear(ctx: *mut czk_ctx, coeffs: *const u64, n: usize, lanes: usize, z: *const u64, quotient: *mut u64, remainder: *mut u64, mem: c_int) -> c_int;
     pub fn czk_poly_evaluate(ctx: *mut czk_ctx, coeffs: *const u64, n: usize, lanes: usize, z: *const u64, values: *mut u64, mem: c_int) -> c_int;
     pub fn czk_poly_evaluate_many(ctx: *mut czk_ctx, count: usize, coeffs: *const *const u64, n: *const usize, lanes: *const usize, z: *const u64, values: *const *mut u64) -> c_int;
