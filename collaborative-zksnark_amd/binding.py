@@ -216,6 +216,15 @@ def _sat_probe_ops():
 LAB_ARITH_PROBE_OPS.update(_sat_probe_ops())
 
 
+LAB_NTT_PASS_SENTINEL = 0xA5A5A5A5   # csrc/lab/ntt_pass_probe.h: every word of the probe's output buffer before the launch
+
+
+class LabNttPassDesc(C.Structure):
+    """struct czk_lab_ntt_pass_desc of csrc/lab/ntt_pass_probe.h"""
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "log_d", "inverse", "K", "s_lo", "first", "last", "prescale", "posttab", "post_mode")] + \
+               [(n, C.c_uint64) for n in ("lanes", "in_len", "in_lane_stride")]
+
+
 class Context:
     """czk_ctx: one GPU + one HIP stream = one MPC party.
 
@@ -332,6 +341,49 @@ class Context:
         out = dict(zip(("c", "W", "nb", "family", "heavy_chunk", "heavy_sub", "exc_cap", "heavy_cap"), (int(v) for v in dims)))
         if not dims_only:
             out.update(buckets=buckets, result=result, **dict(zip(("exc_count", "dirty", "items", "heavy", "overflow"), (int(v) for v in counters))))
+        return out
+
+    def lab_ntt_pass(self, log_d: int, K: int = 0, s_lo: int = 0, data=None, fused: bool = False, inverse: bool = False, first: bool = False,
+                     last: bool = False, lanes: int = 1, in_len: int = 0, in_lane_stride: int = 0, prescale: bool = False, posttab: bool = False,
+                     post_mode: int = 0, addend=None, postconst2=None, dims_only: bool = False):
+        """czk_lab_ntt_pass (csrc/lab/ntt_pass_probe.h, lab library only): ONE pass of the second-generation NTT -- launch_ntt2_pass, or with `fused`
+        launch_ntt2_final_first -- on the buffer `data`, with the domain's own tables.  data: u32 words, (lanes * in_lane_stride, 8) canonical elements
+        for a first pass, (lanes * 2^log_d, scratch words) otherwise; addend: (lanes * 2^log_d, 8) canonical; postconst2: 8 words, one canonical
+        Montgomery element.  Returns the dimensions (scratch format, its element bytes, NTT2_MIN_LOG, NTT2_T, the guard length, pass_plan(log_d) as m, K,
+        s_lo, equal_groups) and, unless dims_only, "out": (lanes * 2^log_d + guard, words) u32, every row the pass did not write still
+        LAB_NTT_PASS_SENTINEL.  A description the kernels could not run safely raises CzkError (CZK_ERR_ARG).  Raises unless the context was
+        opened with lab=True."""
+        if not self._lab:
+            raise RuntimeError("lab_ntt_pass needs Context(lab=True): libczk_hip.so does not export czk_lab_ntt_pass")
+        desc = LabNttPassDesc(mode=1 if fused else 0, log_d=log_d, inverse=int(inverse), K=K, s_lo=s_lo, first=int(first), last=int(last),
+                              prescale=int(prescale), posttab=int(posttab), post_mode=post_mode, lanes=lanes, in_len=in_len, in_lane_stride=in_lane_stride)
+        dims = np.zeros(21, dtype=np.uint64)
+
+        def unpack():
+            d = [int(v) for v in dims]
+            return {"format": d[0], "elem_bytes": d[1], "min_log": d[2], "T": d[3], "guard": d[4], "m": d[5], "equal_groups": bool(d[6]),
+                    "K": d[7:7 + d[5]], "s_lo": d[14:14 + d[5]]}
+
+        self._ck(self._L.czk_lab_ntt_pass(self._h, C.byref(desc), None, C.c_size_t(0), None, None, _ptr(dims), None, C.c_size_t(0)))
+        out = unpack()
+        if dims_only:
+            return out
+        a = np.ascontiguousarray(data, dtype=np.uint32)
+        if a.ndim != 2:
+            raise ValueError("data must have the shape (elements, words per element)")
+        ow = 8 if last and not fused else out["elem_bytes"] // 4
+        res = np.zeros(((lanes << min(log_d, 20)) + out["guard"], ow), dtype=np.uint32)
+        add = None if addend is None else np.ascontiguousarray(addend, dtype=np.uint32)
+        c2 = None if postconst2 is None else np.ascontiguousarray(postconst2, dtype=np.uint32)
+        if c2 is not None and c2.shape != (8,):
+            raise ValueError("postconst2 is one element of 8 words")
+        if add is not None and add.shape != (lanes << log_d, 8):
+            raise ValueError("addend must have the shape (lanes * 2^log_d, 8)")
+        keep = a if a.size else np.zeros((1, 8), dtype=np.uint32)   # an empty first-pass input still needs a pointer
+        self._ck(self._L.czk_lab_ntt_pass(self._h, C.byref(desc), _ptr(keep), C.c_size_t(a.nbytes), _ptr(add), _ptr(c2), _ptr(dims), _ptr(res),
+                                          C.c_size_t(res.nbytes)))
+        out = unpack()
+        out["out"] = res
         return out
 
     def close(self):

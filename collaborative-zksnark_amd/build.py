@@ -15,7 +15,9 @@
                      czk_lab_msm_buckets, which runs the bucket accumulation and reduction (msm.hip's stage bodies) on entry lists the caller wrote and
                      returns every bucket, the rare-path counters and the lane results for tests/test_msm_buckets.py.  csrc/lab/merkle_probe.hip exports
                      czk_lab_merkle_commit, the tree of czk_fr_merkle_commit in the form that was not shipped (one workgroup per subtree), for tools/fri_bench.py
-                     and tests/test_merkle_fri.py.  Loaded by tests through Context(lab=True) and by tools through CZK_LIB_PATH;
+                     and tests/test_merkle_fri.py.  csrc/lab/ntt_pass_probe.hip exports czk_lab_ntt_pass, which launches ONE pass of the second-generation NTT
+                     (ntt_pass.hip: launch_ntt2_pass or the fused launch_ntt2_final_first) on a buffer the caller wrote, at any legal (log_d, s_lo, K), and returns
+                     the whole output buffer with its sentinel-filled guard tail for tests/test_ntt_pass.py.  Loaded by tests through Context(lab=True) and by tools through CZK_LIB_PATH;
                      never by the provers.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container as well as on the GPU box.
@@ -42,10 +44,10 @@ SOURCES = [("core.hip", ["-DCZK_NOINLINE_MUL"]), ("lanes.hip", ["-DCZK_NOINLINE_
 # lab library only: never compiled into, nor linked with, the product library
 LAB_SOURCES = [(os.path.join("lab", "arith_probe.hip"), []), (os.path.join("lab", "sat_probe.hip"), ["-DCZK_NOINLINE_MUL"]),
                (os.path.join("lab", "msm_sort_probe.hip"), ["-DCZK_NOINLINE_MUL"]), (os.path.join("lab", "msm_bucket_probe.hip"), ["-DCZK_NOINLINE_MUL"]),
-               (os.path.join("lab", "merkle_probe.hip"), [])]
+               (os.path.join("lab", "merkle_probe.hip"), []), (os.path.join("lab", "ntt_pass_probe.hip"), [])]
 HEADERS = ["field.h", "curve.h", "czk_internal.h", "call.h", "net.h", "sha256.h", "sha256_dev.h", "blake2s.h", "chacha20.h", "merkle_hash.h", "merkle_tree_plain.h", "pow_tables.h", "msm_acc.h", "fq2p.h", "fq2pu.h", "fqu.h", "fru.h", "fru_constants.inc", "ntt_pass.h", "te.h", "te_constants.inc", "tower.h", "pairing_steps.h", "pairing_constants.inc",
            os.path.join("..", "..", "include", "czk.h")]
-LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h", "arith_probe.h", "sat_probe.h", "merkle_tree_fused.h")]
+LAB_HEADERS = [os.path.join("lab", h) for h in ("msm_aff.h", "fq_safegcd.h", "fqu_il.h", "fqu_mad_il.inc", "fq2u_karatsuba.h", "arith_probe.h", "sat_probe.h", "merkle_tree_fused.h", "ntt_pass_probe.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-pass-failed", "-I" + CSRC]
 # parallel hipcc jobs: CZK_BUILD_JOBS, else the MAX_JOBS a build host sets (a container's os.cpu_count() is the whole machine's), else all cores

@@ -635,34 +635,44 @@ def bfly(B, K, U, x, i, j, w):
     x[j] = B.mul(d, w)
 
 
+class Tws(tuple):
+    """One twiddle per butterfly, indexed as the kernel's arrays are (ntt_pass.hip): radix8 tw[0..4) first stage, tw[4..6) second, tw[6] third; radix4
+    tw[0..2) first stage, tw[2] second; radix8_last tw[1..4) = tw2[1..4) and tw[4] = tw1; radix4_last tw[0] = tw1.  A plain operand instead of a Tws
+    is one twiddle for every butterfly (the interval proof: any canonical twiddle)."""
+
+
+def _tw(tw, i):
+    return tw[i] if isinstance(tw, Tws) else tw
+
+
 def radix8(B, KB, x, tw):
     for k in range(4):
-        bfly(B, KB, 1, x, k, k + 4, tw)
-    bfly(B, 2 * KB, 2, x, 0, 2, tw)
-    bfly(B, 2 * KB, 2, x, 1, 3, tw)
-    bfly(B, 2, 1, x, 4, 6, tw)
-    bfly(B, 2, 1, x, 5, 7, tw)
+        bfly(B, KB, 1, x, k, k + 4, _tw(tw, k))
+    bfly(B, 2 * KB, 2, x, 0, 2, _tw(tw, 4))
+    bfly(B, 2 * KB, 2, x, 1, 3, _tw(tw, 5))
+    bfly(B, 2, 1, x, 4, 6, _tw(tw, 4))
+    bfly(B, 2, 1, x, 5, 7, _tw(tw, 5))
     x[0], x[1] = B.norm(x[0]), B.norm(x[1])
-    bfly(B, 4 * KB, 1, x, 0, 1, tw)
-    bfly(B, 2, 1, x, 2, 3, tw)
-    bfly(B, 4, 2, x, 4, 5, tw)
-    bfly(B, 2, 1, x, 6, 7, tw)
+    bfly(B, 4 * KB, 1, x, 0, 1, _tw(tw, 6))
+    bfly(B, 2, 1, x, 2, 3, _tw(tw, 6))
+    bfly(B, 4, 2, x, 4, 5, _tw(tw, 6))
+    bfly(B, 2, 1, x, 6, 7, _tw(tw, 6))
     for k in (0, 2, 4, 6):
         x[k] = B.norm(x[k])
 
 
 def radix4(B, KB, x, tw):
-    bfly(B, KB, 1, x, 0, 2, tw)
-    bfly(B, KB, 1, x, 1, 3, tw)
-    bfly(B, 2 * KB, 2, x, 0, 1, tw)
-    bfly(B, 2, 1, x, 2, 3, tw)
+    bfly(B, KB, 1, x, 0, 2, _tw(tw, 0))
+    bfly(B, KB, 1, x, 1, 3, _tw(tw, 1))
+    bfly(B, 2 * KB, 2, x, 0, 1, _tw(tw, 2))
+    bfly(B, 2, 1, x, 2, 3, _tw(tw, 2))
     x[0], x[2] = B.norm(x[0]), B.norm(x[2])
 
 
 def radix4_last(B, KB, x, tw):
     d02 = fru_sub(B, KB, 1, x[0], x[2])
     s02 = add_lazy(B, x[0], x[2])
-    bfly(B, KB, 1, x, 1, 3, tw)
+    bfly(B, KB, 1, x, 1, 3, _tw(tw, 0))
     x[0], x[1] = B.norm(add_lazy(B, s02, x[1])), B.norm(fru_sub(B, 2 * KB, 2, s02, x[1]))
     x[2], x[3] = B.norm(add_lazy(B, d02, x[3])), B.norm(fru_sub(B, 2, 1, d02, x[3]))
 
@@ -671,15 +681,15 @@ def radix8_last(B, KB, x, tw):
     d04 = fru_sub(B, KB, 1, x[0], x[4])
     x[0] = add_lazy(B, x[0], x[4])
     for k in range(1, 4):
-        bfly(B, KB, 1, x, k, k + 4, tw)
+        bfly(B, KB, 1, x, k, k + 4, _tw(tw, k))
     d = fru_sub(B, 2 * KB, 2, x[0], x[2])
     x[0] = add_lazy(B, x[0], x[2])
     x[2] = d
-    bfly(B, 2 * KB, 2, x, 1, 3, tw)
+    bfly(B, 2 * KB, 2, x, 1, 3, _tw(tw, 4))
     e = fru_sub(B, 2, 1, d04, x[6])
     x[4] = add_lazy(B, d04, x[6])
     x[6] = e
-    bfly(B, 2, 1, x, 5, 7, tw)
+    bfly(B, 2, 1, x, 5, 7, _tw(tw, 4))
     x[0], x[1] = B.norm(x[0]), B.norm(x[1])
     for i, (K, U) in ((0, (4 * KB, 1)), (2, (2, 1)), (4, (4, 2)), (6, (2, 1))):
         s = add_lazy(B, x[i], x[i + 1])

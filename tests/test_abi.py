@@ -167,7 +167,7 @@ def test_product_library_has_no_environment_switches_and_no_lab_kernels():
     assert " U getenv" not in p and " U secure_getenv" not in p
     assert " U getenv" in q
     lab_only = ("k_affine_round", "k_aff_build_first", "k_accumulate_u2p", "k_accumulate_u_lvl", "czk::k_accumulate<", "czk::k_reduce_level<",
-                "czk_lab_arith_probe", "czk::sat_probe_noinline", "czk_lab_msm_sort")
+                "czk_lab_arith_probe", "czk::sat_probe_noinline", "czk_lab_msm_sort", "czk_lab_ntt_pass")
     for k in lab_only:
         assert k not in p, f"{k} ships in the product library"
         assert k in q, f"{k} missing from the lab library"

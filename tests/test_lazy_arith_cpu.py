@@ -14,6 +14,7 @@ import pytest
 
 import lazy_model as M
 from lazy_model import FQ, FR, P, R, Interval, Iv
+from ntt_pass_model import NTT_CHAINS
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "collaborative-zksnark_amd", "csrc")
 
@@ -239,7 +240,7 @@ def test_closure_xyzzu2_acc_mixed(neg):
 
 
 # the steps ntt_pass.hip instantiates: (kind, KB) per pass shape, W = 1 (canonical inputs) and W = 2 (scratch values < 2 r)
-NTT_CHAINS = {7: [("radix8", 2), ("radix4", 16), ("radix4", 64)], 6: [("radix8", 2), ("radix8", 16)], 5: [("radix8", 2), ("radix4", 16)]}
+# (NTT_CHAINS lives in tests/ntt_pass_model.py, the one table: tests/test_ntt_pass_cpu.py holds it to the kernels' instantiations)
 
 
 @pytest.mark.parametrize("W", [1, 2])
